@@ -15,9 +15,15 @@ documents (weak scaling), `--shard r` replays shard r of the 8-way split on one 
 `--config c2` runs configs[1] (10k documents x 2k insert/remove ops per GPU).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--docs D] [--ops O]
+                    [--full] [--dump-outputs DIR]
 
 Inputs are generated on the GPU (untimed) and stay resident in HBM; the timed region is
-reset + replay kernels only.  Rank 0 prints one JSON line.
+reset + replay kernels only.  Rank 0 prints one JSON line.  A plain run sets up, warms up,
+times the steps and prints the line; `--full` adds everything else the line can report (the
+roofline accounting, the CPU baseline and oracle parity sample, the ingest rates and the
+overlapped ingest pipeline; their fields are null without it).  `--dump-outputs DIR` writes
+what the last timed step left for a caller (per-document checksums, status and a seeded
+sample of document texts) as DIR/<name>.npy, see dump_outputs.
 """
 import argparse
 import json
@@ -49,8 +55,13 @@ def parse():
     ap.add_argument("--ops", type=int, default=0, help="ops per document (default: config)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="CPU baseline threads (0 = every core this process may use)")
     ap.add_argument("--cpu-sample-docs", type=int, default=0, help="0 = all docs of rank 0")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-ingest", action="store_true", help="skip the encode / H2D upload rates")
+    ap.add_argument("--full", action="store_true",
+                    help="also report the roofline, the CPU baseline / oracle parity sample and the ingest rates "
+                         "(a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-ingest", action="store_true", help="--full without the encode / H2D upload rates")
     ap.add_argument("--lds-cap", type=int, default=0, help="segments per document in the LDS tier (0 = default)")
     ap.add_argument("--seg-cap", type=int, default=0, help="flat HBM segments per document (0 = default; sweeps)")
     ap.add_argument("--skew-classes", default="",
@@ -91,6 +102,45 @@ def host_cores():
     except (OSError, ValueError):
         pass
     return max(1, n)
+
+
+DUMP_TEXT_DOCS = 16        # documents whose text --dump-outputs samples
+DUMP_TEXT_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, handles, rank=0, world=1):
+    """`--dump-outputs DIR`: what the last timed step left for a caller of the timed path, as
+    float64 DIR/<name>.npy (rank r of N > 1 writes <name>.rank<r>.npy).  `handles` are the
+    step's MergeTreeBatch handles in launch order; their documents are concatenated.
+      status (docs,)                       mt_get_status per document
+      length, n_segments (docs,)           the checksum record's text length / segment count
+      text_hash, props_hash, delta_hash (docs, 2)
+                                           its 64-bit hashes as (high, low) 32-bit halves
+      text_sample_docs (k,), text_sample_off (k + 1,), text_sample (units,)
+                                           the UTF-16 units of the texts of k documents drawn
+                                           by a fixed seed (7.3 MB in all at 100k documents)
+    The inputs are seeded by the configuration alone, so the same arguments give the same
+    arrays from run to run and from build to build."""
+    os.makedirs(out_dir, exist_ok=True)
+    status = np.concatenate([mt.status() for mt in handles])
+    sums = np.concatenate([mt.checksums() for mt in handles])
+    out = {"status": status, "length": sums["length"], "n_segments": sums["n_segments"]}
+    for k in ("text_hash", "props_hash", "delta_hash"):
+        out[k] = np.stack([sums[k] >> np.uint64(32), sums[k] & np.uint64(0xFFFFFFFF)], axis=1)
+    n = len(status)
+    pick = np.sort(np.random.default_rng(DUMP_TEXT_SEED).choice(n, size=min(n, DUMP_TEXT_DOCS), replace=False))
+    first = np.concatenate([[0], np.cumsum([mt.n_docs for mt in handles])])
+    texts = []
+    for d in pick:
+        h = int(np.searchsorted(first, d, side="right")) - 1
+        texts.append(np.frombuffer(handles[h].get_text(int(d - first[h])).encode("utf-16-le", "surrogatepass"),
+                                   dtype="<u2"))
+    out["text_sample_docs"] = pick
+    out["text_sample_off"] = np.concatenate([[0], np.cumsum([len(t) for t in texts])])
+    out["text_sample"] = np.concatenate(texts) if texts else np.zeros(0)
+    sfx = f".rank{rank}" if world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), np.asarray(a, dtype=np.float64))
 
 
 def launch(args):
@@ -423,12 +473,14 @@ def run_c5(args, cfg, rank, world, local_rank, dist):
     load_ms, tail_ms = mt.last_load_ms(), mt.last_kernel_ms()   # (the last step's, HIP events)
     status = mt.status()
     sums = mt.checksums()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [mt], rank, world)
     if rank != 0:
         return
     n_tail = int(len(idx))
     roofline = c5_roofline(load, counts, tail_arr, sums, n_tail, load_ms, tail_ms)
     cpu = parity = decode = e2e = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         threads = args.cpu_threads or host_cores()
         decode = c5_decode_rate(counts, recs, text, props, mn, cu, cfg["chunk"], min(docs, 4000), threads)
         e2e = c5_end_to_end(mt, counts, recs, text, props, mn, cu, cfg["chunk"], tail_arr, tail, sums, status,
@@ -539,8 +591,10 @@ def run_live(args, rank, world, local_rank, dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     status = mt.status()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [mt], rank, world)
     # parity: every replica ends with the reference participant's text, localSeq and queue
-    sample = list(range(min(docs, 32)))
+    sample = list(range(min(docs, 32))) if args.full else []
     bad = 0
     counts = mt.pending_counts()
     for d in sample:
@@ -550,7 +604,7 @@ def run_live(args, rank, world, local_rank, dist):
     if rank != 0:
         return
     cpu = oracle_sample = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         import pyoracle                            # the checker, timed as the CPU baseline
         # bounded sample: at most ~24M events of CPU work (all of rank 0's 4096 documents)
@@ -588,7 +642,7 @@ def run_live(args, rank, world, local_rank, dist):
                    "parallelism": f"doc-shard x{world}"},
         "cpu_baseline": cpu,
         "reference_calibration": _live_calibration(),
-        "parity": {"status_nonzero": int((status != 0).sum()), "docs_checked": len(sample), "mismatches": bad,
+        "parity": {"status_nonzero": int((status != 0).sum()), "docs_checked": len(sample), "mismatches": bad if args.full else None,
                    "oracle_sample": oracle_sample},
     }))
 
@@ -798,6 +852,45 @@ def ingest_pipeline(caps, device, fx, blobs, threads, slice_docs=3072, n_slices=
                    f"does not fill the GPU as the 100k-document job does)"}
 
 
+def replay_roofline(args, cfg, caps, docs, doc_base, n_ops, host, sums, k_ms, hbm_docs, peaks):
+    """Roofline of the uniform replay: algorithmic bytes per launch (DESIGN.md "Roofline
+    accounting") from the downloaded batch `host` and the final checksums, over the timed
+    steps' mean kernel time; `traffic` is the recorded PMC profile of the matching workload."""
+    ins = host["ops"]["kind"] == 0
+    payload_chars = int(host["ops"]["pos2"][ins].sum())
+    final_bytes = int(sums["n_segments"].astype(np.int64).sum()) * SEG_BYTES + 2 * int(sums["length"].astype(np.int64).sum())
+    alg_bytes = n_ops * (OP_BYTES + RESULT_BYTES) + 2 * payload_chars + final_bytes
+    achieved = alg_bytes / (k_ms / 1000.0)
+    traffic = traffic_raw = None
+    if os.path.exists(PROFILE_PMC):
+        try:
+            pm = json.load(open(PROFILE_PMC)).get(args.config, {})
+            if pm.get("docs") == docs and pm.get("ops") == cfg["ops"] and pm.get("seed_base", 0) == doc_base:
+                traffic = pm.get("hbm_bytes_per_launch")
+                traffic_raw = pm.get("hbm_bytes_per_launch_raw")
+        except Exception:
+            traffic = None
+    return {
+        "bound": "hbm", "achieved": round(achieved / 1e9, 3), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+        "frac": achieved / HBM_PEAK, "traffic": traffic,
+        "traffic_raw": traffic_raw,
+        "traffic_correction": ("2 x FETCH_SIZE + WRITE_SIZE: on gfx950 FETCH_SIZE counts 64 B per 128-byte read "
+                               "request; measured 1/2 on this kernel's page-window, uid-map and text read "
+                               "patterns (profiles/r4/fetch_calibration.json) and cross-checked by the L2 "
+                               "request counts (profiles/pmc_summary.json)") if traffic is not None else None,
+        "kernel": ("k_replay<TierLdsT<false>> (first ops) + k_replay_paged<TierPagedT<false>> (rest)"
+                   if caps.get("page_capacity", 0) > 0 else
+                   "k_replay<TierLdsT<false>> + k_replay<TierGlbT<false>> (HBM-tier hand-over)"),
+        "kernel_ms": round(k_ms, 3), "alg_bytes_per_launch": alg_bytes,
+        "docs_replayed_from_hbm": hbm_docs,
+        "paged_peaks": peaks,
+        "paged_caps": {"lds": [caps.get("lds_page_capacity"), caps.get("lds_unsettled_capacity"),
+                               caps.get("lds_page_heap_capacity")],
+                       "hbm": [caps.get("page_capacity"), caps.get("unsettled_capacity"),
+                               caps.get("page_heap_capacity")]},
+    }
+
+
 def run_replay(args, cfg, rank, world, local_rank, dist):
     """Uniform replay (c2 / c3 / c4): the default line, BASELINE configs[2]."""
     from fluidframework_amd import MergeTreeBatch
@@ -821,7 +914,7 @@ def run_replay(args, cfg, rank, world, local_rank, dist):
     # 7-10 % slower in its host encode (the line vs tools/ingest_probe.py, profiles/r6); rank 0
     # only, like the CPU baseline (the host's cores are shared by the ranks)
     pipeline = None
-    with_ingest = not args.no_ingest and rank == 0
+    with_ingest = args.full and not args.no_ingest and rank == 0
     if with_ingest:
         fx, blobs = c3_logs()
         pipeline = ingest_pipeline(caps, local_rank, fx, blobs, host_cores())
@@ -878,6 +971,8 @@ def run_replay(args, cfg, rank, world, local_rank, dist):
     status = mt.status()
     sums = mt.checksums()
     replay_consistent = bool(np.array_equal(sums, gen_sums)) and int((status != 0).sum()) == 0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [mt], rank, world)
 
     threads = args.cpu_threads or host_cores()
     # the only collective: all-gather of per-document checksums over RCCL/xGMI, verified
@@ -887,7 +982,7 @@ def run_replay(args, cfg, rank, world, local_rank, dist):
         local = torch.empty(docs * 32, dtype=torch.uint8, device="cuda")
         mt.checksums_device(local.data_ptr())
         shards = verify_shards(dist, rank, world, docs_total, cfg, local, gen_sums, torch.device("cuda", local_rank),
-                               args.verify_per_rank, threads)
+                               args.verify_per_rank if args.full else 0, threads)
         ok = torch.tensor([1 if replay_consistent else 0], device="cuda")
         dist.all_reduce(ok, op=dist.ReduceOp.MIN)
         replay_consistent = bool(ok.item())
@@ -900,29 +995,16 @@ def run_replay(args, cfg, rank, world, local_rank, dist):
     ms_per_step = elapsed * 1000.0 / args.steps
     value = total_ops * args.steps / elapsed
 
-    # roofline: algorithmic bytes per launch (DESIGN.md "Roofline accounting")
-    host = batch.download()
-    ins = host["ops"]["kind"] == 0
-    payload_chars = int(host["ops"]["pos2"][ins].sum())
-    final_bytes = int(sums["n_segments"].astype(np.int64).sum()) * SEG_BYTES + 2 * int(sums["length"].astype(np.int64).sum())
-    alg_bytes = n_ops * (OP_BYTES + RESULT_BYTES) + 2 * payload_chars + final_bytes
-    k_ms = float(np.mean(kernel_ms))
-    achieved = alg_bytes / (k_ms / 1000.0)
+    # everything below the timed figures reads the batch back from the device (--full only)
+    host = batch.download() if args.full else None
+    roofline = replay_roofline(args, cfg, caps, docs, doc_base, n_ops, host, sums, float(np.mean(kernel_ms)),
+                               hbm_docs, peaks) if args.full else None
     ingest = None if not with_ingest else ingest_rates(mt, host, ms_per_step / 1000.0, caps, local_rank,
                                                              pipeline)
-    traffic = traffic_raw = None
-    if os.path.exists(PROFILE_PMC):
-        try:
-            pm = json.load(open(PROFILE_PMC)).get(args.config, {})
-            if pm.get("docs") == docs and pm.get("ops") == cfg["ops"] and pm.get("seed_base", 0) == doc_base:
-                traffic = pm.get("hbm_bytes_per_launch")
-                traffic_raw = pm.get("hbm_bytes_per_launch_raw")
-        except Exception:
-            traffic = None
 
     cpu = None
     parity = None
-    if not args.no_cpu and rank == 0:
+    if args.full and not args.no_cpu and rank == 0:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         import pyoracle                            # the checker, timed as the CPU baseline
         # bounded sample: about 100M ops of CPU work, ~10 s on 16 host threads (all of C2's
@@ -981,25 +1063,7 @@ def run_replay(args, cfg, rank, world, local_rank, dist):
             "docs_total": docs_total, "docs_per_gpu": docs, "ops_per_doc": cfg["ops"], "ops_per_step": total_ops,
             "parallelism": f"doc-shard x{world}",
         },
-        "roofline": {
-            "bound": "hbm", "achieved": round(achieved / 1e9, 3), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-            "frac": achieved / HBM_PEAK, "traffic": traffic,
-            "traffic_raw": traffic_raw,
-            "traffic_correction": ("2 x FETCH_SIZE + WRITE_SIZE: on gfx950 FETCH_SIZE counts 64 B per 128-byte read "
-                                   "request; measured 1/2 on this kernel's page-window, uid-map and text read "
-                                   "patterns (profiles/r4/fetch_calibration.json) and cross-checked by the L2 "
-                                   "request counts (profiles/pmc_summary.json)") if traffic is not None else None,
-            "kernel": ("k_replay<TierLdsT<false>> (first ops) + k_replay_paged<TierPagedT<false>> (rest)"
-                       if caps.get("page_capacity", 0) > 0 else
-                       "k_replay<TierLdsT<false>> + k_replay<TierGlbT<false>> (HBM-tier hand-over)"),
-            "kernel_ms": round(k_ms, 3), "alg_bytes_per_launch": alg_bytes,
-            "docs_replayed_from_hbm": hbm_docs,
-            "paged_peaks": peaks,
-            "paged_caps": {"lds": [caps.get("lds_page_capacity"), caps.get("lds_unsettled_capacity"),
-                                   caps.get("lds_page_heap_capacity")],
-                           "hbm": [caps.get("page_capacity"), caps.get("unsettled_capacity"),
-                                   caps.get("page_heap_capacity")]},
-        },
+        "roofline": roofline,
         "cpu_baseline": cpu,
         "ingest": ingest,
         "parity": {"replay_equals_generation": replay_consistent, "oracle_sample": parity,

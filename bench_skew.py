@@ -175,7 +175,9 @@ def run_skew(args, cfg, rank, world, local_rank, dist, bench):
     # timed class by class with every thread busy (documents taken longest first as threads
     # free up).  The job's CPU time is each class's messages at its own rate, summed.
     mism, sampled, cpu = 0, 0, None
-    if rank == 0 and not args.no_cpu:
+    if getattr(args, "dump_outputs", ""):
+        bench.dump_outputs(args.dump_outputs, [r["mt"] for r in runs], rank, world)
+    if rank == 0 and getattr(args, "full", False) and not args.no_cpu:
         from concurrent.futures import ThreadPoolExecutor
         sys.path.insert(0, os.path.join(bench.REPO, "oracle"))
         import pyoracle

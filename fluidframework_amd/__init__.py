@@ -71,6 +71,7 @@ class MergeTreeBatch:
         if not self.h:
             raise RuntimeError("mt_create failed (no HIP device visible, or out of device memory)")
         self.n_docs = n_docs
+        self.device = device
 
     def close(self):
         if self.h:
@@ -501,6 +502,71 @@ class MergeTreeBatch:
         self._check(self.lib.mt_get_text(self.h, doc, _native.ptr(buf), n.value, ctypes.byref(n)),
                     "mt_get_text")
         return buf[: n.value].tobytes().decode("utf-16-le", errors="surrogatepass")
+
+    # bulk / ranged text (mt_get_texts): SharedString.getText(start, end), getTextWithPlaceholders
+    # and getTextRangeWithPlaceholders (sharedString.ts:222-236) for many documents in one launch
+    def _text_queries(self, docs, start, end, placeholder):
+        """(n, docs, start, end, marker_unit) as mt_get_texts takes them; scalars broadcast."""
+        if isinstance(placeholder, str):
+            units = np.frombuffer(placeholder.encode("utf-16-le", errors="surrogatepass"), dtype=np.uint16)
+            if len(units) > 1:
+                raise ValueError("get_texts: the placeholder is empty or one UTF-16 unit")
+            placeholder = int(units[0]) if len(units) else 0
+        if docs is not None:
+            docs = np.ascontiguousarray(docs, dtype=np.uint32).reshape(-1)
+        n = len(docs) if docs is not None else self.n_docs
+        if start is not None:
+            start = np.ascontiguousarray(np.broadcast_to(np.asarray(start, dtype=np.int32), (n,)))
+        if end is not None:
+            end = np.asarray([-1 if e is None else e for e in end] if isinstance(end, (list, tuple)) else end)
+            end = np.ascontiguousarray(np.broadcast_to(end.astype(np.int32), (n,)))
+        return n, docs, start, end, int(placeholder)
+
+    def get_texts_raw(self, docs=None, start=None, end=None, placeholder=""):
+        """(off, units): query q's UTF-16 units are units[off[q]:off[q + 1]]."""
+        n, docs, start, end, mu = self._text_queries(docs, start, end, placeholder)
+        off = np.zeros(n + 1, dtype=np.int64)
+        args = (self.h, n, _native.ptr(docs), _native.ptr(start), _native.ptr(end), mu, _native.ptr(off))
+        self._check(self.lib.mt_get_texts(*args, None, 0), "mt_get_texts")
+        units = np.zeros(max(int(off[n]), 1), dtype=np.uint16)
+        self._check(self.lib.mt_get_texts(*args, _native.ptr(units), int(off[n])), "mt_get_texts")
+        return off, units[: int(off[n])]
+
+    def get_texts(self, docs=None, start=None, end=None, placeholder=""):
+        """The observer-view text of each query (doc, start, end): every document when docs is
+        None, whole documents when start / end are None (an end of -1 or None: the document's
+        length).  start and end are clamped into [0, length].  placeholder "": markers give
+        nothing; one UTF-16 unit (" " in getTextWithPlaceholders): each marker gives that unit."""
+        off, units = self.get_texts_raw(docs, start, end, placeholder)
+        raw = units.tobytes()
+        return [raw[2 * int(off[q]): 2 * int(off[q + 1])].decode("utf-16-le", errors="surrogatepass")
+                for q in range(len(off) - 1)]
+
+    def get_texts_device(self, docs=None, start=None, end=None, placeholder="", out=None):
+        """get_texts_raw with the results left on the handle's device: (off, units) torch tensors
+        (int64 [n + 1], int16 holding the UTF-16 units).  out: an int16 tensor on that device to
+        fill (at least the result's size); units is then its leading slice.  (A process that
+        uses torch on the GPU imports it before it creates its first handle, as bench.py does:
+        the replay library then shares torch's HIP runtime.)"""
+        import torch
+        n, docs, start, end, mu = self._text_queries(docs, start, end, placeholder)
+        dev = torch.device("cuda", self.device)
+        off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        args = (self.h, n, _native.ptr(docs), _native.ptr(start), _native.ptr(end), mu, ctypes.c_void_p(off.data_ptr()))
+        if out is None:
+            self._check(self.lib.mt_get_texts_device(*args, None, 0), "mt_get_texts_device")
+            out = torch.empty(max(int(off[n]), 1), dtype=torch.int16, device=dev)
+        elif out.dtype != torch.int16 or out.device != dev or not out.is_contiguous():
+            raise ValueError("get_texts_device: out is a contiguous int16 tensor on the handle's device")
+        self._check(self.lib.mt_get_texts_device(*args, ctypes.c_void_p(out.data_ptr()), out.numel()),
+                    "mt_get_texts_device")
+        return off, out[: int(off[n])]
+
+    def last_text_ms(self):
+        """Device time (ms) of the last get_texts call's counting pass and gather."""
+        out = np.zeros(2, dtype=np.float32)
+        self._check(self.lib.mt_last_text_ms(self.h, _native.ptr(out)), "mt_last_text_ms")
+        return float(out[0]), float(out[1])
 
     def get_segments(self, doc):
         nr, nl = ctypes.c_uint32(), ctypes.c_uint32()

@@ -457,6 +457,182 @@ __global__ void __launch_bounds__(MT_WAVE) k_checksum(DevState st, mt_checksum *
     }
 }
 
+// ---------------------------------------------------------------- bulk text read-out
+// MergeTreeTextHelper.getText(currentSeq, local client, placeholder, start, end)
+// (MT/textSegment.ts:154-186, gatherText :241-263) for many (doc, start, end) queries: one
+// wave per query, the document's segments in chunks of 64 (one lane per segment).  A
+// segment at observer position pos of visible length l gives the units [max(pos, start),
+// min(pos + l, end)) -- text.substring(start - pos, end - pos) -- and a marker in the range
+// gives marker_unit (nothing when 0).  end < 0: the document's length; both ends clamp.
+struct TextQuery {
+    int doc, s, e;
+};
+__device__ static TextQuery text_query(const DevState &st, int q, const uint32_t *docs, const int32_t *start,
+                                       const int32_t *end) {
+    TextQuery Q;
+    Q.doc = docs ? (int)docs[q] : q;
+    Q.s = start ? max(start[q], 0) : 0;
+    const int e = end ? end[q] : -1;
+    Q.e = e < 0 ? 0x7FFFFFFF : e;
+    if (Q.doc < 0 || Q.doc >= st.n_docs) Q.e = 0;   // (the host refuses these)
+    return Q;
+}
+// lane's segment i of a chunk clipped to [s, e): units it contributes, its first unit's offset
+// in the arena half (-1: a marker); pos is the chunk's first position, advanced past it
+__device__ __forceinline__ int text_clip(const v4i *A, const v4u *Bv, int i, int n, int s, int e, int marker_unit,
+                                         int &pos, int &src) {
+    int l = 0;
+    uint32_t toff = 0;
+    bool marker = false;
+    if (i < n) {
+        l = obs_len(A[i]);
+        const v4u b = Bv[i];
+        marker = (b.z & MT_MARKER_BIT) != 0;
+        toff = b.x;
+    }
+    const int incl = wave_scan_incl(l);
+    const int p0 = pos + incl - l;
+    pos += __builtin_amdgcn_readlane(incl, 63);
+    const int lo = max(p0, s), hi = min(p0 + l, e);
+    int units = max(hi - lo, 0);
+    if (marker) units = marker_unit ? units : 0;
+    src = marker ? -1 : (int)toff + (lo - p0);
+    return units;
+}
+__global__ void __launch_bounds__(MT_WAVE) k_text_count(DevState st, int nq, const uint32_t *docs, const int32_t *start,
+                                                        const int32_t *end, int marker_unit, int64_t *len) {
+    const int q = blockIdx.x;
+    if (q >= nq) return;
+    const TextQuery Q = text_query(st, q, docs, start, end);
+    int total = 0;
+    if (Q.s < Q.e) {
+        const DocHdr h = st.hdr[Q.doc];
+        const SegRanges R = seg_ranges(st, Q.doc, h);
+        int pos = 0;
+        for (int r = 0; r < R.count() && pos < Q.e; r++) {
+            const v4i *A;
+            const v4u *Bv;
+            int n;
+            R.get(r, A, Bv, n);
+            for (int base = 0; base < n && pos < Q.e; base += MT_WAVE) {
+                int src;
+                total += text_clip(A, Bv, base + lane(), n, Q.s, Q.e, marker_unit, pos, src);
+            }
+        }
+        total = wave_sum(total);
+    }
+    if (lane() == 0) len[q] = total;
+}
+// off[0..n]: exclusive prefix sums of len[0..n) (one block; the device variant's offsets)
+__global__ void __launch_bounds__(1024) k_text_scan(const int64_t *len, int n, int64_t *off) {
+    __shared__ int64_t part[1024];
+    const int t = threadIdx.x, per = (n + 1023) / 1024;
+    const int lo = min(t * per, n), hi = min(lo + per, n);
+    int64_t s = 0;
+    for (int i = lo; i < hi; i++) s += len[i];
+    part[t] = s;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int64_t v = t >= o ? part[t - o] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int64_t run = part[t] - s;
+    for (int i = lo; i < hi; i++) {
+        off[i] = run;
+        run += len[i];
+    }
+    if (t == 1023) off[n] = part[1023];
+}
+// Writes query q's units at out[off[q] ..).  Per chunk the 64 clipped segments' destination
+// offsets (a wave scan) and sources go to LDS and the chunk's output units are dealt across
+// the lanes, which find their unit's segment by a 6-step search of the offsets: lanes follow
+// output units, so short segments keep the wave busy.  In the body a lane produces the two
+// units of a 4-byte-aligned destination word and stores one dword; a chunk that ends on the
+// first half of a word carries that unit into the next one, so single units are stored only at
+// a query's odd head and its tail.
+// kPerSeg: the k_extract-style copy instead (a wave loop per segment, unit stores), kept for
+// the A/B in tools/readout_probe.py.
+template <bool kPerSeg>
+__global__ void __launch_bounds__(MT_WAVE) k_text_gather(DevState st, int nq, const uint32_t *docs,
+                                                         const int32_t *start, const int32_t *end, int marker_unit,
+                                                         const int64_t *off, uint16_t *out) {
+    __shared__ int s_dst[MT_WAVE], s_src[MT_WAVE];
+    const int q = blockIdx.x;
+    if (q >= nq) return;
+    const TextQuery Q = text_query(st, q, docs, start, end);
+    if (Q.s >= Q.e || off[q + 1] == off[q]) return;
+    const DocHdr h = st.hdr[Q.doc];
+    const SegRanges R = seg_ranges(st, Q.doc, h);
+    const PagedBase ar = doc_paged(st, Q.doc);   // (the arenas of the document's region)
+    const uint16_t *tb = ar.text + (size_t)h.text_half * ar.T;
+    const uint32_t T = (uint32_t)ar.T;
+    uint16_t *o = out + off[q];
+    const int64_t room = off[q + 1] - off[q];    // never write past the query's slot
+    const int odd = (int)(((uintptr_t)o >> 1) & 1);   // the slot starts on the second half of a word
+    // unit u of the chunk (units of segment sg start at s_dst[sg])
+    auto unit_at = [&](int u) -> uint32_t {
+        int sg = 0;
+#pragma unroll
+        for (int step = MT_WAVE / 2; step > 0; step >>= 1)
+            if (s_dst[sg + step] <= u) sg += step;
+        const int sr = s_src[sg];
+        if (sr < 0) return (uint32_t)marker_unit;
+        const uint32_t ix = (uint32_t)sr + (uint32_t)(u - s_dst[sg]);
+        return ix < T ? tb[ix] : 0u;
+    };
+    int pos = 0;
+    int64_t done = 0;        // units of the query produced so far (the carried one included)
+    bool carry = false;      // unit done - 1 is the first half of a word not yet stored
+    uint32_t carry_v = 0;
+    for (int r = 0; r < R.count() && pos < Q.e; r++) {
+        const v4i *A;
+        const v4u *Bv;
+        int n;
+        R.get(r, A, Bv, n);
+        for (int base = 0; base < n && pos < Q.e; base += MT_WAVE) {
+            int src;
+            const int units = text_clip(A, Bv, base + lane(), n, Q.s, Q.e, marker_unit, pos, src);
+            const int incl = wave_scan_incl(units);
+            int tot = __builtin_amdgcn_readlane(incl, 63);
+            if (done + tot > room) tot = (int)(room - done);   // (the state cannot change between the passes)
+            if (tot <= 0) continue;
+            if constexpr (kPerSeg) {
+                for (int sg = 0; sg < MT_WAVE; sg++) {
+                    const int un = bcast(units, sg), d0 = bcast(incl, sg) - un, sr = bcast(src, sg);
+                    for (int k = lane(); k < un && d0 + k < tot; k += MT_WAVE) {
+                        const uint32_t ix = (uint32_t)sr + (uint32_t)k;
+                        o[done + d0 + k] = sr < 0 ? (uint16_t)marker_unit : (ix < T ? tb[ix] : (uint16_t)0);
+                    }
+                }
+                done += tot;
+                continue;
+            }
+            __syncthreads();   // the previous chunk's readers are done with the LDS arrays
+            s_dst[lane()] = incl - units;
+            s_src[lane()] = src;
+            __syncthreads();
+            // chunk-local unit u lies at o[done + u]; u = -1 is the carried unit
+            int u0 = carry ? -1 : 0;
+            if (!carry && ((done + odd) & 1)) {   // the query's odd head (done == 0 here)
+                if (lane() == 0) o[done] = (uint16_t)unit_at(0);
+                u0 = 1;
+            }
+            const int npair = (tot - u0) >> 1;
+            for (int k = lane(); k < npair; k += MT_WAVE) {
+                const int u = u0 + 2 * k;
+                const uint32_t a = u < 0 ? carry_v : unit_at(u), b = unit_at(u + 1);
+                *(uint32_t *)(o + done + u) = a | (b << 16);
+            }
+            carry = ((tot - u0) & 1) != 0;
+            if (carry) carry_v = unit_at(tot - 1);
+            done += tot;
+        }
+    }
+    if (!kPerSeg && carry && lane() == 0) o[done - 1] = (uint16_t)carry_v;   // the tail
+}
+
 // ============================================================================ host side
 // ---------------------------------------------------------------- live-client reconnect
 // regeneratePendingOp for the oldest pending segment group of one document (one wave):
@@ -604,6 +780,8 @@ struct mt_handle {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_load = nullptr, ev_load1 = nullptr;
     bool load_timed = false;   // ev_load / ev_load1 bracket the last snapshot load's kernels
+    hipEvent_t ev_txt[4] = {nullptr, nullptr, nullptr, nullptr};   // mt_get_texts: around its counting pass, around its gather
+    int txt_timed = 0;         // 1: the counting pass was bracketed, 2: the gather as well
     // documents per workgroup of the LDS-tier replay (env MT_WPG=2 for two): measured on C2
     // the CU saturates at 16 resident documents (16 -> 18 per CU: 61.8 -> 64.6 ms)
     int wpg = 1;
@@ -974,6 +1152,8 @@ void mt_destroy(mt_handle *h) {
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->ev_load) hipEventDestroy(h->ev_load);
     if (h->ev_load1) hipEventDestroy(h->ev_load1);
+    for (hipEvent_t e : h->ev_txt)
+        if (e) hipEventDestroy(e);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
 }
@@ -2563,6 +2743,118 @@ int mt_get_text(mt_handle *h, uint32_t doc, uint16_t *out, uint32_t cap, uint32_
         }
     }
     if (out_len) *out_len = n;
+    return 0;
+}
+
+// mt_get_texts / mt_get_texts_device: the counting pass, the prefix sums (on the host for host
+// results, as mt_extract_snapshots takes them; k_text_scan for device results), the gather.
+namespace {
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() {
+        if (p) hipFree(p);
+    }
+};
+}   // namespace
+static int get_texts(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
+                     uint16_t marker_unit, int64_t *off, uint16_t *out, void *off_dev, void *out_dev, uint64_t cap,
+                     bool device) {
+    if (!h || n > 0x7FFFFFFFu || (device ? !off_dev : !off)) return MT_E_INVALID;
+    if (!docs && n > h->n_docs) return MT_E_INVALID;
+    if (docs)
+        for (uint32_t q = 0; q < n; q++)
+            if (docs[q] >= h->n_docs) return MT_E_INVALID;
+    HIPCHK(h, hipSetDevice(h->device));
+    SETTLE(h);
+    h->txt_timed = 0;
+    if (n == 0) {
+        if (device)
+            HIPCHK(h, hipMemset(off_dev, 0, 8));
+        else
+            off[0] = 0;
+        return 0;
+    }
+    for (hipEvent_t &e : h->ev_txt)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    // one allocation: [docs | start | end] (n words each, absent ones stay unused), len[n], off[n + 1]
+    DevBuf args, d_out;
+    const size_t words = (size_t)n * 3 + (n & 1);   // (the 8-byte arrays stay aligned)
+    HIPCHK(h, hipMalloc(&args.p, words * 4 + ((size_t)n * 2 + 1) * 8));
+    uint32_t *d_docs = (uint32_t *)args.p;
+    int32_t *d_start = (int32_t *)args.p + n, *d_end = (int32_t *)args.p + 2 * (size_t)n;
+    int64_t *d_len = (int64_t *)((uint32_t *)args.p + words), *d_off = d_len + n;
+    if (docs) HIPCHK(h, hipMemcpy(d_docs, docs, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (start) HIPCHK(h, hipMemcpy(d_start, start, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (end) HIPCHK(h, hipMemcpy(d_end, end, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (!docs) d_docs = nullptr;
+    if (!start) d_start = nullptr;
+    if (!end) d_end = nullptr;
+    HIPCHK(h, hipEventRecord(h->ev_txt[0], h->stream));
+    hipLaunchKernelGGL(k_text_count, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start, d_end,
+                       (int)marker_unit, d_len);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev_txt[1], h->stream));
+    int64_t total = 0;
+    if (device) {
+        d_off = (int64_t *)off_dev;
+        hipLaunchKernelGGL(k_text_scan, dim3(1), dim3(1024), 0, h->stream, d_len, (int)n, d_off);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(&total, d_off + n, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    } else {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(off + 1, d_len, (size_t)n * 8, hipMemcpyDeviceToHost));
+        off[0] = 0;
+        for (uint32_t q = 0; q < n; q++) off[q + 1] += off[q];
+        total = off[n];
+    }
+    h->txt_timed = 1;
+    if (device ? !out_dev : !out) return 0;   // sizing only
+    if (cap < (uint64_t)total) {
+        h->err = "mt_get_texts: the output holds " + std::to_string(cap) + " units, the results need " +
+                 std::to_string(total);
+        return MT_E_OVERFLOW;
+    }
+    if (total == 0) return 0;
+    uint16_t *d_text = (uint16_t *)out_dev;
+    if (!device) {
+        HIPCHK(h, hipMemcpy(d_off, off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMalloc(&d_out.p, (size_t)total * 2));
+        d_text = (uint16_t *)d_out.p;
+    }
+    // MT_TEXT_PER_SEGMENT=1: the per-segment copy (the A/B of tools/readout_probe.py)
+    const char *ps = getenv("MT_TEXT_PER_SEGMENT");
+    const bool per_seg = ps && ps[0] == '1';
+    HIPCHK(h, hipEventRecord(h->ev_txt[2], h->stream));
+    if (per_seg)
+        hipLaunchKernelGGL(k_text_gather<true>, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start,
+                           d_end, (int)marker_unit, d_off, d_text);
+    else
+        hipLaunchKernelGGL(k_text_gather<false>, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start,
+                           d_end, (int)marker_unit, d_off, d_text);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev_txt[3], h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->txt_timed = 2;
+    if (!device) HIPCHK(h, hipMemcpy(out, d_text, (size_t)total * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int mt_get_texts(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
+                 uint16_t marker_unit, int64_t *off, uint16_t *out, uint64_t cap) {
+    return get_texts(h, n, docs, start, end, marker_unit, off, out, nullptr, nullptr, cap, false);
+}
+
+int mt_get_texts_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
+                        uint16_t marker_unit, void *off_dev, void *out_dev, uint64_t cap) {
+    return get_texts(h, n, docs, start, end, marker_unit, nullptr, nullptr, off_dev, out_dev, cap, true);
+}
+
+int mt_last_text_ms(mt_handle *h, float *out) {
+    if (!h || !out) return MT_E_INVALID;
+    out[0] = out[1] = 0.f;
+    if (h->txt_timed >= 1) HIPCHK(h, hipEventElapsedTime(&out[0], h->ev_txt[0], h->ev_txt[1]));
+    if (h->txt_timed >= 2) HIPCHK(h, hipEventElapsedTime(&out[1], h->ev_txt[2], h->ev_txt[3]));
     return 0;
 }
 

@@ -510,6 +510,56 @@ napi_value GetText(napi_env env, napi_callback_info info) {
     return s;
 }
 
+// getTexts(h, docs|null, start|null, end|null, markerUnit) -> string[]   (mt_get_texts:
+// MergeTreeTextHelper.getText(currentSeq, local client, placeholder, start, end) for many
+// queries in one launch.  docs: Uint32Array (null: every document); start / end: Int32Array
+// of the same length (null: whole documents; end < 0: the document's length); markerUnit: 0
+// for the "" placeholder, else the UTF-16 unit each marker contributes.)
+napi_value GetTexts(napi_env env, napi_callback_info info) {
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return nullptr;
+    Handle *hd = get_handle(env, argv[0]);
+    if (!hd) return nullptr;
+    void *ptrs[3] = {nullptr, nullptr, nullptr};
+    size_t lens[3] = {0, 0, 0};
+    const napi_typedarray_type want[3] = {napi_uint32_array, napi_int32_array, napi_int32_array};
+    for (int i = 0; i < 3; i++) {
+        napi_valuetype vt;
+        NAPI_CALL(env, napi_typeof(env, argv[1 + i], &vt));
+        if (vt == napi_null || vt == napi_undefined) continue;
+        napi_typedarray_type t;
+        napi_value ab;
+        size_t off;
+        if (napi_get_typedarray_info(env, argv[1 + i], &t, &lens[i], &ptrs[i], &ab, &off) != napi_ok || t != want[i]) {
+            napi_throw_type_error(env, nullptr, "getTexts: docs is a Uint32Array, start and end are Int32Arrays (or null)");
+            return nullptr;
+        }
+        if (!ptrs[i]) ptrs[i] = &lens[i];   // (an empty array: any non-null pointer, never read)
+    }
+    const size_t n = ptrs[0] ? lens[0] : mt_num_docs(hd->h);
+    if ((ptrs[1] && lens[1] != n) || (ptrs[2] && lens[2] != n)) {
+        napi_throw_range_error(env, nullptr, "getTexts: start and end hold one entry per query");
+        return nullptr;
+    }
+    const uint16_t mu = (uint16_t)get_i32(env, argv[4]);
+    std::vector<int64_t> off(n + 1);
+    int rc = mt_get_texts(hd->h, (uint32_t)n, (const uint32_t *)ptrs[0], (const int32_t *)ptrs[1],
+                          (const int32_t *)ptrs[2], mu, off.data(), nullptr, 0);
+    if (rc) return throw_rc(env, hd, rc, "mt_get_texts");
+    std::vector<uint16_t> buf((size_t)off[n] ? (size_t)off[n] : 1);
+    rc = mt_get_texts(hd->h, (uint32_t)n, (const uint32_t *)ptrs[0], (const int32_t *)ptrs[1],
+                      (const int32_t *)ptrs[2], mu, off.data(), buf.data(), (uint64_t)off[n]);
+    if (rc) return throw_rc(env, hd, rc, "mt_get_texts");
+    napi_value arr;
+    NAPI_CALL(env, napi_create_array_with_length(env, n, &arr));
+    for (size_t q = 0; q < n; q++) {
+        napi_value s;
+        NAPI_CALL(env, napi_create_string_utf16(env, (const char16_t *)buf.data() + off[q], (size_t)(off[q + 1] - off[q]), &s));
+        NAPI_CALL(env, napi_set_element(env, arr, (uint32_t)q, s));
+    }
+    return arr;
+}
+
 // getPropRuns(h, doc) -> {runs: Uint32Array (start, length, record) x n, records: Uint32Array}
 napi_value GetPropRuns(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -780,7 +830,7 @@ napi_value Init(napi_env env, napi_value exports) {
     } fns[] = {{"create", Create},         {"destroy", Destroy},           {"loadInitialText", LoadInitialText},
                  {"startCollaboration", StartCollaboration},
                {"applyOps", ApplyOps},     {"loadSnapshots", LoadSnapshots},     {"status", Status},             {"getLength", GetLength},
-               {"getText", GetText},       {"getPropRuns", GetPropRuns},   {"getDeltaLog", GetDeltaLog},
+               {"getText", GetText},       {"getTexts", GetTexts},         {"getPropRuns", GetPropRuns},   {"getDeltaLog", GetDeltaLog},
                {"deltaLogReset", DeltaLogReset},
                {"maintenanceCounts", MaintenanceCounts},
                {"checksums", Checksums},   {"lastKernelMs", LastKernelMs}, {"numDocs", NumDocs},

@@ -289,6 +289,16 @@ class GpuMergeTreeBatch {
         return out;
     }
 
+    /**
+     * The text of many documents in one launch (mt_get_texts; SharedString.getText of each):
+     * docs is a list of document indices (repeats allowed), every document when omitted.
+     * A failed document answers from the state it stopped in.
+     */
+    getTexts(docs) {
+        this.flush();
+        return native.getTexts(this.h, docs === undefined || docs === null ? null : Uint32Array.from(docs), null, null, 0);
+    }
+
     lastKernelMs() { return native.lastKernelMs(this.h); }
 
     dispose() { native.destroy(this.h); }
@@ -460,9 +470,50 @@ class GpuClient {
 
     getLength() { this._sync(); return native.getLength(this.batch.h, this.doc); }
 
-    getText() { this._sync(); return native.getText(this.batch.h, this.doc); }
+    /**
+     * SharedString.getText(start?, end?) (sharedString.ts:222-225).  With a range the text is
+     * assembled on the GPU (mt_get_texts): start and end are clamped into [0, length] (the
+     * reference's results for arguments outside 0 <= start <= end <= length are not reproduced).
+     */
+    getText(start, end) {
+        this._sync();
+        if (start === undefined && end === undefined) { return native.getText(this.batch.h, this.doc); }
+        return this._textRange(start, end, 0);
+    }
 
-    createTextHelper() { return { getText: () => this.getText() }; }
+    /** SharedString.getTextWithPlaceholders (sharedString.ts:229-232): a space per marker. */
+    getTextWithPlaceholders() { this._sync(); return this._textRange(undefined, undefined, 0x20); }
+
+    /** SharedString.getTextRangeWithPlaceholders(start, end) (sharedString.ts:233-236). */
+    getTextRangeWithPlaceholders(start, end) { this._sync(); return this._textRange(start, end, 0x20); }
+
+    _textRange(start, end, markerUnit) {
+        return native.getTexts(this.batch.h, Uint32Array.of(this.doc), Int32Array.of(start === undefined ? 0 : start),
+            Int32Array.of(end === undefined ? -1 : end), markerUnit)[0];
+    }
+
+    /**
+     * MergeTreeTextHelper (textSegment.ts:154-186): getText(refSeq, clientId, placeholder = "",
+     * start?, end?) in the replica's own view -- (currentSeq, the local client), the only view
+     * SharedString asks text in; any other view throws, and so does a placeholder longer than
+     * one UTF-16 unit (the "*" mode included: getTextRangeWithMarkers is not offered).
+     */
+    createTextHelper() {
+        return {
+            getText: (refSeq, clientId, placeholder = "", start, end) => {
+                if (refSeq === undefined && clientId === undefined) { return this.getText(); }
+                if (refSeq !== this.getCurrentSeq() || clientId !== this.getClientId()) {
+                    throw new Error("merge-tree replay: text is read in the replica's own view only " +
+                        `(refSeq ${this.getCurrentSeq()}, client ${this.getClientId()}), not (${refSeq}, ${clientId})`);
+                }
+                if (typeof placeholder !== "string" || placeholder.length > 1 || placeholder === "*") {
+                    throw new Error("merge-tree replay: the marker placeholder is \"\" or one UTF-16 unit other than \"*\"");
+                }
+                this._sync();
+                return this._textRange(start, end, placeholder.length ? placeholder.charCodeAt(0) : 0);
+            },
+        };
+    }
 
     /** Client.getPropertiesAtPosition (client.ts:1011-1025). */
     getPropertiesAtPosition(pos) {

@@ -282,6 +282,39 @@ int mt_batch_download(const mt_batch *b, int64_t *doc_op_off, mt_op_rec *ops, ui
 int mt_get_status(mt_handle *h, int32_t *out_status);                 /* [n_docs] */
 int mt_get_length(mt_handle *h, uint32_t doc, uint32_t *out);
 int mt_get_text(mt_handle *h, uint32_t doc, uint16_t *out, uint32_t cap, uint32_t *out_len);
+/* MergeTreeTextHelper.getText(currentSeq, local client, placeholder, start, end)
+   (MT/textSegment.ts:154-186, 241-263) for n queries in one launch, assembled on the device.
+   A query is (doc, start, end) in the observer view, the only view SharedString asks text in.
+   docs NULL: documents 0..n-1 (n <= n_docs).  start / end NULL: whole documents; end[q] < 0: the
+   document's length.  Positions count markers (length 1) like every other position.
+   marker_unit 0: markers contribute nothing (placeholder ""); otherwise each marker in the
+   range contributes that one UTF-16 unit (" " is what the reference passes).  The "*"
+   placeholder mode ("\n" + marker.toString()) is not offered.
+   off[n + 1] always receives the prefix sums of the result lengths.  out NULL: sizing only.
+   Otherwise out[off[q] .. off[q + 1]) is query q's text; cap < off[n]: MT_E_OVERFLOW, nothing
+   written to out.
+   - Visibility: a segment is visible when its removed seq is MT_RSEQ_NONE, as in mt_get_text and
+     mt_get_length.  On a live handle the local client's unacked inserts are in and its
+     pending removes are out.
+   - Clamping: start and end are clamped into [0, length]; start >= end gives an empty result.
+     (The reference's behaviour for arguments outside 0 <= start <= end <= length is not
+     reproduced.)
+   - A segment partly inside the range contributes text.substring(start - pos, end - pos).
+   - Failed documents answer from the state they stopped in, as mt_get_text does.
+   - The same document may appear in many queries, in any order; a doc >= n_docs is
+     MT_E_INVALID.
+   - The call settles the handle first (waits for the stream and a pending growth step), like
+     every read-out. */
+int mt_get_texts(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start,
+                 const int32_t *end, uint16_t marker_unit, int64_t *off, uint16_t *out, uint64_t cap);
+/* The same with off (int64[n + 1]) and out (uint16[cap]) in device memory on the handle's
+   device (e.g. torch tensors); docs / start / end stay host arrays.  The prefix sums are taken
+   on the device; the call returns once the results are written. */
+int mt_get_texts_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start,
+                        const int32_t *end, uint16_t marker_unit, void *off_dev, void *out_dev, uint64_t cap);
+/* Device time of the most recent mt_get_texts / mt_get_texts_device call's two kernels (HIP
+   events): out[0] the counting pass, out[1] the gather (0 after a sizing call). */
+int mt_last_text_ms(mt_handle *h, float *out /* [2] */);
 /* Observer-visible property runs: rows of (start, length, props_record_index) plus the
    records [count, (key, value)*].  Returns counts through the out pointers. */
 int mt_get_prop_runs(mt_handle *h, uint32_t doc, uint32_t *runs, uint32_t cap_runs,

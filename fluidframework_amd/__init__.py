@@ -466,6 +466,13 @@ class MergeTreeBatch:
         return dict(pages=int(out[0]), unsettled=int(out[1]), heap=int(out[2]), segments=int(out[3]),
                     tight_handovers=int(out[4]))
 
+    def last_zamboni(self):
+        """Zamboni's scours of the last batch / generation outside the staged page: done in place
+        on the page in HBM, or through the window after all (mt_last_zamboni)."""
+        out = np.zeros(2, dtype=np.uint32)
+        self._check(self.lib.mt_last_zamboni(self.h, _native.ptr(out)), "mt_last_zamboni")
+        return {"in_place": int(out[0]), "fallback": int(out[1])}
+
     def last_grown(self):
         """The last batch's growth step (mt_last_grown): documents moved to larger paged
         capacities, rounds, documents in the big region and its capacities."""

@@ -1865,6 +1865,157 @@ TD int scour_block(DocT<T> &d, int s, int e) {
     return keep;
 }
 
+// The lane-parallel plan of scour_range over rows held in registers: lane k holds entry k
+// (a, b) when `in`; `start` is the lane of the first entry of this lane's block, `pend` (live
+// documents) holds the entry back.  An unknown trailing-newline flag of a merge candidate is
+// resolved by the lane's own text read into b.w (nl_res: the lane did; the caller stores it
+// where its rows live).  big: a join longer than MT_GRAN -- the serial per-block form decides.
+// Both the window's scour (rows read from LDS) and the paged in-place scour (rows fetched from
+// HBM, mt_paged.h pg_scour_inplace) plan here, so the scour rules exist once.
+struct ScourPlan {
+    u64 m_join, m_unlink, m_surv;
+    bool big;
+};
+TD ScourPlan scour_plan(DocT<T> &d, const v4i &a, v4u &b, bool in, bool pend, int start, bool &nl_res) {
+    const int k = lane();
+    const bool removed = a.z != MT_RSEQ_NONE;
+    const bool marker = (b.z & MT_MARKER_BIT) != 0;
+    const bool cand = in && !pend && !removed && a.y <= d.min_seq;
+    // resolve unknown trailing-newline flags of merge candidates (lanes in parallel)
+    nl_res = cand && !marker && a.x > 0 && !(b.w & SEGF_NL_KNOWN);
+    if (ballot(nl_res)) {
+        P2_T0(9)
+        gsync_rd();
+        if (nl_res) {
+            const uint16_t ch = text_base(d, d.text_half)[b.x + a.x - 1];
+            b.w = (b.w & ~SEGF_NL) | SEGF_NL_KNOWN | (ch == '\n' ? SEGF_NL : 0u);
+        }
+        P2_T1(9)
+    }
+    const u64 m_cand = ballot(cand);
+    const u64 m_mark = ballot(in && marker);
+    const u64 m_nl = ballot(in && (b.w & SEGF_NL) != 0);
+    const uint32_t pprops = (uint32_t)__shfl_up((int)b.y, 1, MT_WAVE);
+    const bool pc = k > 0 && ((m_cand >> (k - 1)) & 1ull);
+    const bool pm = k > 0 && ((m_mark >> (k - 1)) & 1ull);
+    const bool pn = k > 0 && ((m_nl >> (k - 1)) & 1ull);
+#ifdef MT_NO_Q4
+    const u64 m_nm = 0;
+#else
+    const u64 m_nm = ballot(in && (b.w & SEGF_NOMATCH) != 0);
+#endif
+    const bool nm = ((m_nm >> k) & 1ull) || (k > 0 && ((m_nm >> (k - 1)) & 1ull));
+    bool join = cand && pc && k != start && !marker && !pm && !pn && a.x > 0;
+    if (join && (nm || pprops != b.y)) join = match_props(d, pprops, b.y, nm);
+    ScourPlan p;
+    p.m_join = ballot(join);
+    p.big = ballot(join && a.x > MT_GRAN) != 0;
+    const bool unlink = in && !pend && removed && a.z <= d.min_seq;
+    p.m_unlink = ballot(unlink);
+    p.m_surv = ballot(in && !unlink && !join);
+    return p;
+}
+// The plan's merge groups: a keeper (m_grp) is a survivor whose next entry joins it.  L:
+// inclusive lengths; gend: the lane of the group's last member; glen: the merged length;
+// totc: the arena units the merges take at most (each group's text and its slack).
+struct ScourGroups {
+    u64 m_grp;
+    int L, gend, glen, totc;
+};
+__device__ __forceinline__ ScourGroups scour_groups(const v4i &a, bool in, u64 m_join, u64 m_surv) {
+    const int k = lane();
+    const u64 above = (k < 63) ? (m_join >> (k + 1)) : 0ull;
+    ScourGroups g;
+    g.m_grp = ballot(((m_surv >> k) & 1ull) && (above & 1ull));
+    g.L = g.gend = g.glen = g.totc = 0;
+    if (g.m_grp) {
+        // group length of each keeper: inclusive lengths up to the group's last member
+        g.L = wave_scan_incl(in ? a.x : 0);
+        g.gend = k + __ffsll((long long)~above) - 1;   // last member (above has a 0)
+        const int Lend = __shfl(g.L, g.gend < MT_WAVE ? g.gend : MT_WAVE - 1, MT_WAVE);
+        g.glen = Lend - g.L + (in ? a.x : 0);
+        for (u64 q = g.m_grp; q; q &= q - 1) {
+            const int gl = bcast(g.glen, first_lane(q));
+            g.totc += gl + text_slack(gl);
+        }
+    }
+    return g;
+}
+// Text merges group by group, on rows in registers (as the arena holds them now: after any
+// compaction); the room for g.totc units is the caller's to ensure.  A keeper copied to the
+// arena top reserves slack after its text so that later appends land in place
+// (TextSegment.append :70-85 is a string concatenation; this keeps it amortised O(1)).
+// The keepers' lanes (g.m_grp) leave with their merged length, offset and flags in a / b.
+TD void scour_merge(DocT<T> &d, v4i &a, v4u &b, bool in, const ScourGroups &g) {
+    const int k = lane();
+    const v4i a0 = a;
+    const v4u bm = b;
+    const int L = g.L;
+    for (u64 q = g.m_grp; q; q &= q - 1) {
+        const int kk = first_lane(q);
+        const int gk = bcast(g.glen, kk);
+        const int ge = bcast(g.gend, kk);
+        const v4u bk = v4u{(uint32_t)bcast((int)bm.x, kk), (uint32_t)bcast((int)bm.y, kk),
+                           (uint32_t)bcast((int)bm.z, kk), (uint32_t)bcast((int)bm.w, kk)};
+        const int ak = bcast(a0.x, kk);
+        const uint32_t kslack = bk.w >> SEGF_SLACK_SHIFT;
+        // members kk+1..ge: contiguity of their text after the keeper's
+        const bool mem = k > kk && k <= ge;
+        const int Lm = L - (in ? a0.x : 0);       // exclusive prefix of lengths
+        const int Lk = bcast(L, kk) - ak;         // keeper's exclusive prefix
+        const int rel = Lm - Lk;                  // member's offset inside the merged text
+        const bool contig_lane = !mem || (int)bm.x == (int)bk.x + rel;
+        const bool contig = !ballot(!contig_lane);
+        const int add = gk - ak;
+        const uint32_t lastw = (uint32_t)bcast((int)bm.w, ge);
+        // the merged text is newline-free when the keeper's and every member's are
+        const uint32_t nonl = (bk.w & SEGF_NONL) && !ballot(mem && !(bm.w & SEGF_NONL)) ? SEGF_NONL : 0u;
+        uint32_t newoff = bk.x, newslack = lastw >> SEGF_SLACK_SHIFT;
+        if (!contig) {
+            int dst;
+            bool move_keeper = false;
+            if ((uint32_t)add <= kslack) {                       // append into the slack
+                dst = (int)bk.x + ak;
+                newslack = kslack - (uint32_t)add;
+            } else if ((int)bk.x + ak == d.text_top) {          // keeper ends at the top
+                dst = d.text_top;
+                newslack = (uint32_t)text_slack(gk);
+                d.text_top += add + (int)newslack;
+            } else {                                            // move keeper + appends
+                newoff = (uint32_t)d.text_top;
+                dst = d.text_top + ak;
+                move_keeper = true;
+                newslack = (uint32_t)text_slack(gk);
+                d.text_top += gk + (int)newslack;
+            }
+            GLB_AS uint16_t *tb = text_base(d, d.text_half);
+            // gather: unit t of the merged text (t < gk); units < ak come from the keeper
+            const int t0 = move_keeper ? 0 : ak;
+            for (int base = t0; base < gk; base += MT_WAVE) {
+                const int t = base + lane();
+                int src = 0;
+                if (t < ak) {
+                    src = (int)bk.x + t;
+                } else {
+                    // member whose exclusive prefix (relative) is <= t: scan members
+                    for (int j = kk + 1; j <= ge; j++) {
+                        const int rj = bcast(Lm, j) - Lk;
+                        if (t >= rj) src = bcast((int)bm.x, j) + (t - rj);
+                    }
+                }
+                uint16_t ch = 0;
+                if (t < gk) ch = tb[src];
+                if (t < gk) tb[(move_keeper ? (int)newoff : dst - ak) + t] = ch;
+            }
+        }
+        if (k == kk) {
+            a.x = gk;
+            b.x = newoff;
+            b.w = (lastw & (SEGF_NL_KNOWN | SEGF_NL)) | nonl | (newslack << SEGF_SLACK_SHIFT);
+        }
+    }
+}
+
 // scourNode :1322-1398 applied, in order, to the consecutive leaf blocks [b0, b0 + nbk)
 // whose segments start at index s -- one block for zamboniSegments, every child of the
 // parent for pack.  Lane-parallel: entry j is appended to the run before it iff both are
@@ -1890,43 +2041,18 @@ TD int scour_range(DocT<T> &d, int s, int b0, int nbk) {
             st += cntr(d, 0, b0 + q);
         }
     }
-    const bool removed = a.z != MT_RSEQ_NONE;
-    const bool marker = (b.z & MT_MARKER_BIT) != 0;
     bool pend = false;   // held: in a pending segment group (scourNode :1328)
     if constexpr (T::kLive) pend = in && pq_any(pq_get(d, in ? s + k : s));
-    const bool cand = in && !pend && !removed && a.y <= d.min_seq;
+    ScourPlan pl = ScourPlan{0ull, 0ull, 0ull, false};
     if (!serial) {
-        // resolve unknown trailing-newline flags of merge candidates (lanes in parallel)
-        const bool need_nl = cand && !marker && a.x > 0 && !(b.w & SEGF_NL_KNOWN);
-        if (ballot(need_nl)) {
-            P2_T0(9)
-            gsync_rd();
-            if (need_nl) {
-                const uint16_t ch = text_base(d, d.text_half)[b.x + a.x - 1];
-                b.w = (b.w & ~SEGF_NL) | SEGF_NL_KNOWN | (ch == '\n' ? SEGF_NL : 0u);
-                d.Bv[s + k].w = b.w;
-            }
+        bool nl_res;
+        pl = scour_plan(d, a, b, in, pend, start, nl_res);
+        if (ballot(nl_res)) {
+            if (nl_res) d.Bv[s + k].w = b.w;
             wsync<T>();
-            P2_T1(9)
         }
+        serial = pl.big;
     }
-    const u64 m_cand = ballot(cand);
-    const u64 m_mark = ballot(in && marker);
-    const u64 m_nl = ballot(in && (b.w & SEGF_NL) != 0);
-    const uint32_t pprops = (uint32_t)__shfl_up((int)b.y, 1, MT_WAVE);
-    const bool pc = k > 0 && ((m_cand >> (k - 1)) & 1ull);
-    const bool pm = k > 0 && ((m_mark >> (k - 1)) & 1ull);
-    const bool pn = k > 0 && ((m_nl >> (k - 1)) & 1ull);
-#ifdef MT_NO_Q4
-    const u64 m_nm = 0;
-#else
-    const u64 m_nm = ballot(in && (b.w & SEGF_NOMATCH) != 0);
-#endif
-    const bool nm = ((m_nm >> k) & 1ull) || (k > 0 && ((m_nm >> (k - 1)) & 1ull));
-    bool join = cand && pc && k != start && !marker && !pm && !pn && a.x > 0;
-    if (join && (nm || pprops != b.y)) join = match_props(d, pprops, b.y, nm);
-    const u64 m_join = ballot(join);
-    if (!serial && ballot(join && a.x > MT_GRAN)) serial = true;
     if (serial) {   // rare: per-block serial plan (scour_block)
         int pos = s, kept_all = 0;
         for (int q = 0; q < nbk; q++) {
@@ -1941,39 +2067,30 @@ TD int scour_range(DocT<T> &d, int s, int b0, int nbk) {
         }
         return kept_all;
     }
-    const bool unlink = in && !pend && removed && a.z <= d.min_seq;
-    const bool surv = in && !unlink && !join;
+    const u64 m_join = pl.m_join, m_surv = pl.m_surv;
+    const bool surv = (m_surv >> k) & 1ull;
     if (T::kLog) {   // scourNode's UNLINK / APPEND events :1343-1373
-        d.m_unlink += __popcll(ballot(unlink));
+        d.m_unlink += __popcll(pl.m_unlink);
         d.m_append += __popcll(m_join);
     }
-    const u64 m_surv = ballot(surv);
-    scour_events(d, a, b, ballot(unlink), m_join, m_surv, s, tot, start);
-    const u64 above = (k < 63) ? (m_join >> (k + 1)) : 0ull;
-    const u64 m_grp = ballot(surv && (above & 1ull));
+    scour_events(d, a, b, pl.m_unlink, m_join, m_surv, s, tot, start);
+    const ScourGroups g = scour_groups(a, in, m_join, m_surv);
     P2_T0(10)
-    if (m_grp) {
+    if (g.m_grp) {
         mark_dirty(d, s);
-        // group length of each keeper: inclusive lengths up to the group's last member
-        const int L = wave_scan_incl(in ? a.x : 0);
-        const int gend = k + __ffsll((long long)~above) - 1;   // last member (above has a 0)
-        const int Lend = __shfl(L, gend < MT_WAVE ? gend : MT_WAVE - 1, MT_WAVE);
-        const int glen = Lend - L + (in ? a.x : 0);
-        int totc = 0;
-        for (u64 g = m_grp; g; g &= g - 1) {
-            const int gl = bcast(glen, first_lane(g));
-            totc += gl + text_slack(gl);
-        }
-        if (!text_ensure(d, totc)) return tot;
+        if (!text_ensure(d, g.totc)) return tot;
         gsync_rd();
-        // text merges group by group.  A keeper copied to the arena top reserves slack after
-        // its text so that later appends land in place (TextSegment.append :70-85 is a
-        // string concatenation; this keeps it amortised O(1)).
-        for (u64 g = m_grp; g; g &= g - 1) {
-            const int kk = first_lane(g);
-            const int gk = bcast(glen, kk);
-            const int ge = bcast(gend, kk);
-            const v4u bk = uni4(d.Bv[s + kk]);   // fresh: text_ensure may have compacted
+        // text merges group by group, on the window's rows (fresh: text_ensure may have
+        // compacted); scour_merge is the same arithmetic on rows in registers -- a fix to
+        // slack, contiguity or move-keeper goes into both.  (Calling scour_merge here, with the
+        // rows reloaded after text_ensure and the keepers written back, was built: holding the
+        // rows across the groups took P_C3 from 8 to 22 spilled VGPRs, tools/regs.sh.)
+        const int L = g.L;
+        for (u64 q = g.m_grp; q; q &= q - 1) {
+            const int kk = first_lane(q);
+            const int gk = bcast(g.glen, kk);
+            const int ge = bcast(g.gend, kk);
+            const v4u bk = uni4(d.Bv[s + kk]);
             const int ak = uni(d.A[s + kk].x);
             const uint32_t kslack = bk.w >> SEGF_SLACK_SHIFT;
             // members kk+1..ge: contiguity of their text after the keeper's

@@ -478,6 +478,12 @@ __device__ __forceinline__ void pg_peaks(const DevState &st, PagedDoc<T> &pd, in
         atomicMax(st.stats + 9, (uint32_t)pk_ut);
         atomicMax(st.stats + 10, (uint32_t)pk_heap);
         atomicMax(st.stats + 11, (uint32_t)ns);
+        // zamboni's scours outside the window: in place / through the window (mt_last_zamboni)
+        if constexpr (pg_zinplace<T>()) {
+            const uint32_t zi = pg_zcount(pd)[0], zf = pg_zcount(pd)[1];
+            if (zi) atomicAdd(st.stats + 16, zi);
+            if (zf) atomicAdd(st.stats + 17, zf);
+        }
     }
 }
 // Replay of the documents flagged by the LDS tier (retry[doc]) in the paged layout: a

@@ -44,7 +44,8 @@
 template <class T> struct PagedDoc {
     DocT<T> w;    // window: one page staged in LDS (first member: see pdoc)
     DocT<T> up;   // levels >= 1 of the tree (level 1 = pages, counted in leaf blocks)
-    LDS_AS PageMeta *meta;    // [PP] by page id (T::kHM: null -- gmeta instead)
+    LDS_AS PageMeta *meta;    // [PP] by page id (T::kHM: null -- gmeta instead); two counters
+                              // follow it (pg_zcount)
     GLB_AS PageMeta *gmeta;   // T::kHM: the page metadata in HBM, where it lives for the launch
                               // (observer length, leaf-block counts, needsScour flags)
     LDS_AS int *pvl;          // [PP] by level-1 position: view length in the cached view (vr, vc)
@@ -140,7 +141,8 @@ static __host__ __device__ inline PagedLayout paged_layout(int PP, int PH, int U
     o = (o + 7u) & ~7u;
     L.offUO = o; o += packed ? 8u * MT_PK_MASKS + MT_PK_MASKS / 8 : ((((uint32_t)ob * UT) + 7u) & ~7u);
     L.offHeap = o; o += 8u * (PH + 1);
-    L.offMeta = o; o += hm ? 0u : (uint32_t)sizeof(PageMeta) * PP;
+    // (+ 8: the document's in-place / window scour counts, pg_zcount)
+    L.offMeta = o; o += hm ? 0u : (uint32_t)sizeof(PageMeta) * PP + 8u;
     L.offUpage = o; o += packed ? 0u : (2u * UT + 3u) & ~3u;
     L.offCob = o; o += hm ? 8u * (uint32_t)((PP + 63) / 64) + 4u * 64 : 4u * PP;   // cob + cdl + sob, or pvl
     L.offWscr = o; o += 64u * 4;
@@ -1448,6 +1450,127 @@ TD void pg_pack1_impl(PagedDoc<T> &pd, int pos) {
 
 // ------------------------------------------------------------------ zamboni (paged)
 // zamboniSegments :1455-1511 with the heap in LDS and the uid -> page map in HBM.
+//
+// In-place scour.  Message pages are spread over the whole document, so the segment zamboni
+// pops almost always lies on a page Z other than the window's P.  Moving the window there
+// (flush P, stage Z in LDS) and back at the next message costs two window moves per message
+// for one leaf block of <= 8 rows.  pg_scour_inplace scours that block on Z's rows in
+// registers (lane i = slot i, as pg_win_fetch leaves them) and stores what changed straight
+// to Z in HBM; P stays staged and dirty.  Tiers without the delta log, live state or HBM
+// metadata only (-DMT_NO_ZINPLACE compiles the path out: same-tree A/B).
+//
+// Equality with the window path: after it, Z's rows in HBM and its PageMeta are what the
+// window path followed by Z's flush would have left -- the same plan (scour_plan), the same
+// merges (scour_merge), survivors at the block's front, the tail shifted left, the block's
+// count and cleared flag, the page's segment count; the observer length is unchanged by a
+// scour (unlinked rows have none, merges keep the sum) and no segment changes page, so the uid
+// map stands.  (Up to one bit that carries no state: a trailing-newline flag resolved for an
+// unchanged survivor before the first changed slot is not stored here, while the window's flush
+// writes from the block's start; the flag caches the text's last unit and is resolved again.)
+// Every later step reaches a page either through the window (pd.cur) or through
+// HBM, never both, and scours touch settled segments only, so the unsettled table and every
+// view are unaffected (the invariant PagedDoc.tdirty states).  Whatever would make the window
+// path do more than that -- the serial per-block plan, a pack of the page's leaf blocks, an
+// arena compaction -- is detected before anything is stored, and the window path runs on the
+// page exactly as HBM holds it.
+// The document's counts of zamboni's scours outside the window: [0] done in place, [1] through
+// the window after all (mt_last_zamboni).  In LDS behind the page metadata: two more uniform
+// registers through the op loop cost P_C3 32 spilled VGPRs (tools/regs.sh).
+TD LDS_AS uint32_t *pg_zcount(PagedDoc<T> &pd) { return (LDS_AS uint32_t *)(pd.meta + pd.PP); }
+template <class T> constexpr bool pg_zinplace() {
+#ifdef MT_NO_ZINPLACE
+    return false;
+#else
+    return !T::kLog && !T::kHM && !T::kLive;
+#endif
+}
+// Scours the leaf block of page pg (!= pd.cur, nseg > 0) that holds segment uid.  true: the
+// window path has to run (nothing was written); false: done, or nothing to do.
+TD bool pg_scour_inplace(PagedDoc<T> &pd, int pg, uint32_t uid) {
+    DocT<T> &w = pd.w;
+    const int k = lane();
+    const int n = uni(pm_nseg(pd, pg)), nb = uni(pm_nblk(pd, pg));
+    // (the overlap masks are fetched only where rows move: two fewer registers live through
+    // the plan)
+    v4i a = v4i{0, 0, 0, 0};
+    v4u b = v4u{0, 0, 0, 0};
+    if (k < n) {
+        a = pd.gA[(size_t)pg * MT_PG_SLOTS + k];
+        b = pd.gB[(size_t)pg * MT_PG_SLOTS + k];
+    }
+    uint32_t bc, f2;
+    pm_blocks(pd, pg, bc, f2);
+    bc = (uint32_t)uni((int)bc);
+    f2 = (uint32_t)uni((int)f2);
+    const u64 hit = ballot(k < n && (b.z & ~MT_MARKER_BIT) == uid);
+    if (!hit) {   // the segment is gone
+        PG_CNT(19)
+        return false;
+    }
+    const int i = first_lane(hit);
+    int q = 0, bstart = 0;
+    while (q < nb && q < 8 && i >= bstart + pm_bc_of(bc, q)) {
+        bstart += pm_bc_of(bc, q);
+        q++;
+    }
+    if (q >= nb || q >= 8) {
+        FAIL_INTERNAL(w);
+        return false;
+    }
+    if (pm_fl_of(f2, q) == 0) {   // already scoured
+        PG_CNT(20)
+        return false;
+    }
+    const int cnt = pm_bc_of(bc, q);
+    if (pd.up.depth < 2 || bstart + cnt > n) return true;
+    const bool in = k >= bstart && k < bstart + cnt;
+    bool nl_res;
+    const ScourPlan pl = scour_plan(w, a, b, in, false, bstart, nl_res);
+    const int keep = __popcll(pl.m_surv);
+    // the serial per-block plan, or a pack of the page's leaf blocks: the window path's
+    if (pl.big || (keep < cnt && keep < MT_HALF)) return true;
+    const ScourGroups g = scour_groups(a, in, pl.m_join, pl.m_surv);
+    if (g.m_grp && w.text_top + g.totc > w.T_cap) return true;   // the merges need a compaction
+    PG_CNT(21)
+    PG_CNT(37)
+    if (k == 0) pg_zcount(pd)[0]++;
+    const uint32_t nbc = (bc & ~(15u << (4 * q))) | ((uint32_t)keep << (4 * q));
+    const uint32_t nf2 = (f2 & ~(3u << (2 * q))) | (1u << (2 * q));   // needsScour = false
+    if (g.m_grp) {
+        gsync_rd();
+        scour_merge(w, a, b, in, g);
+    }
+    if (keep < cnt || g.m_grp) {
+        // survivors to the block's front, the tail moved left; rows from the first changed slot
+        // on go to HBM (a resolved newline flag travels only with a row that is written anyway,
+        // as in the window, where it does not mark the slot dirty)
+        const u64 blk = ((1ull << cnt) - 1ull) << bstart;
+        const u64 chg = g.m_grp | (blk & ~pl.m_surv);
+        const int first = __ffsll((long long)chg) - 1;
+        const bool surv = (pl.m_surv >> k) & 1ull;
+        const int dst = in ? bstart + __popcll(pl.m_surv & ((1ull << k) - 1ull)) : k - (cnt - keep);
+        const bool st = k < n && k >= first && (in ? surv : keep < cnt);
+        const bool mv = st && dst != k;
+        u64 o = 0;
+        if (mv) o = pd.gO[(size_t)pg * MT_PG_SLOTS + k];
+        asm volatile("" : "+v"(o));   // (every lane's load before any lane's store)
+        if (st) {
+            pd.gA[(size_t)pg * MT_PG_SLOTS + dst] = a;
+            pd.gB[(size_t)pg * MT_PG_SLOTS + dst] = b;
+        }
+        if (mv) pd.gO[(size_t)pg * MT_PG_SLOTS + dst] = o;
+    } else {
+        PG_CNT(38)
+    }
+    if (k == 0) {
+        pd.meta[pg].bc = nbc;
+        pd.meta[pg].flg2 = (uint16_t)nf2;
+        pm_set_ns(pd, pg, n - (cnt - keep), nb);
+    }
+    wsync<T>();
+    return false;
+}
+
 TD void pg_zamboni_impl(PagedDoc<T> &pd);
 TD void pg_zamboni(PagedDoc<T> &pd) {
     PG_T0(12)
@@ -1514,6 +1637,11 @@ TD void pg_zamboni_impl(PagedDoc<T> &pd) {
                 if (pg == pd.cur || pg >= pd.PP || uni(pm_nseg(pd, pg)) == 0) {
                     PG_CNT(19)
                     continue;
+                }
+                if constexpr (pg_zinplace<T>()) {
+                    if (!pg_scour_inplace(pd, pg, uid)) continue;
+                    if (w.status) return;
+                    if (lane() == 0) pg_zcount(pd)[1]++;
                 }
                 PG_CNT(18)
                 pg_win_switch(pd, pg);
@@ -1763,7 +1891,16 @@ TD bool pg_room(PagedDoc<T> &pd, const mt_op_rec &op) {
     // a narrow tier holds overlap slots 1..32 only
     if (T::kOvlBits < 64 && op.kind == MT_OP_REMOVE && oslot_short(pd.w, op_cli(op))) return false;
     if (T::kPacked && op.seq - pd.sbase > 65000) return false;   // the packed table's seq offsets
-    if (pd.ut_n + pd.wgrow + ut_b > pd.UT) return false;
+    if (pd.ut_n + pd.wgrow + ut_b > pd.UT) {
+        // With in-place scours the op's window stays dirty across the message boundary: ut_n
+        // still counts its entries that have settled since, and wgrow the finished message's
+        // bound.  The flush rebuilds them (its adds fit: ut_n + wgrow <= UT held when they were
+        // bounded), and the bound is evaluated once more before the document is handed on.
+        if (!pg_zinplace<T>() || pd.cur < 0 || !pd.dirty) return false;
+        pd.opbound = 0;   // no message is in progress
+        pg_win_flush(pd);
+        if (pd.w.status || pd.ut_n + pd.wgrow + ut_b > pd.UT) return false;
+    }
     if constexpr (T::kPacked) {
         // the sparse mask table: every entry this message (and the window's rebuild) may add
         // could carry a mask; a shortage hands the document on here instead of failing a
@@ -2422,6 +2559,9 @@ TD void pg_setup(PagedDoc<T> &pd, const DevState &st, int doc, LDS_AS uint8_t *s
     pd.zuid = 0;
     pd.zpv = 0;
     pd.press = 0;
+    if constexpr (!T::kHM) {
+        if (lane() == 0) pg_zcount(pd)[0] = pg_zcount(pd)[1] = 0;
+    }
     pd.ovf_top = MT_OVF_HDR;
     pd.ovf_last = 0;
     pd.ovf_maxn = 0;

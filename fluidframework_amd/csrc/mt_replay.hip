@@ -1077,7 +1077,7 @@ mt_handle *mt_create(uint32_t n_docs, const mt_options *opt) {
     alloc((void **)&h->d_sums, N * sizeof(mt_checksum));
     alloc((void **)&st.retry, N * sizeof(int32_t));
     alloc((void **)&st.resume, N * sizeof(int64_t));
-    alloc((void **)&st.stats, 16 * sizeof(uint32_t));
+    alloc((void **)&st.stats, MT_STATS_WORDS * sizeof(uint32_t));
 #ifdef MT_PROF
     alloc((void **)&st.prof, 128 * sizeof(unsigned long long));
     if (ok) ok = hipMemset(st.prof, 0, 128 * sizeof(unsigned long long)) == hipSuccess;
@@ -1371,7 +1371,7 @@ int mt_batch_apply_async(mt_handle *h, const mt_batch *b) {
     }
     h->st.order = b->order;   // (its launches and its growth step's)
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemsetAsync(h->st.stats, 0, 16 * sizeof(uint32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->st.stats, 0, MT_STATS_WORDS * sizeof(uint32_t), h->stream));
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
     if (h->lds.S > 0) {
         // LDS tier for every document; the ones that outgrow it are flagged and replayed
@@ -2041,6 +2041,14 @@ int mt_last_paged_peaks(mt_handle *h, uint32_t *out) {
     return 0;
 }
 
+int mt_last_zamboni(mt_handle *h, uint32_t *out) {
+    if (!h || !out) return MT_E_INVALID;
+    HIPCHK(h, hipSetDevice(h->device));
+    SETTLE(h);
+    HIPCHK(h, hipMemcpy(out, h->st.stats + 16, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int mt_apply_ops(mt_handle *h, const int64_t *doc_op_off, const mt_op_rec *ops, uint64_t n_ops,
                  const uint16_t *text, uint64_t text_len, const uint32_t *props,
                  uint64_t props_len) {
@@ -2441,7 +2449,7 @@ mt_batch *mt_generate_docs(mt_handle *h, const mt_gen_cfg *cfg, uint32_t doc_ind
     if (ok && doc_ids)
         ok = hipMalloc(&d_ids, N * 4) == hipSuccess && hipMemcpy(d_ids, doc_ids, N * 4, hipMemcpyHostToDevice) == hipSuccess;
     h->st.gen_ids = d_ids;
-    if (ok) ok = hipMemsetAsync(h->st.stats, 0, 16 * sizeof(uint32_t), h->stream) == hipSuccess;
+    if (ok) ok = hipMemsetAsync(h->st.stats, 0, MT_STATS_WORDS * sizeof(uint32_t), h->stream) == hipSuccess;
     if (ok) {
         const int gw = 2 * (cfg->writers + 1);
         if (h->lds.S > 0) {

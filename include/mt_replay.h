@@ -240,6 +240,12 @@ int mt_last_hbm_docs(mt_handle *h, uint32_t *out);
    out[5] = {pages, unsettled-table entries, zamboni heap entries, segments, documents handed
    from the tight to the full-capacity paged tier}; sizing aid for the paged capacities. */
 int mt_last_paged_peaks(mt_handle *h, uint32_t *out);
+/* Zamboni's scours of the most recent batch (or generation) whose segment lay on a page other
+   than the one staged in LDS, summed over the paged documents: out[2] = {scoured in place on
+   the page in HBM, scoured through the window after all (the serial plan, a pack of the page's
+   leaf blocks or a text compaction was needed)}.  Tiers with a delta log or with their page
+   metadata in HBM always move the window and count neither. */
+int mt_last_zamboni(mt_handle *h, uint32_t *out);
 
 /* Growth step of the most recent batch (mt_sync runs it; see mt_options: the paged
    capacities are where documents start, not a limit): out[6] = {documents handed to it,

@@ -28,6 +28,8 @@ mt.lib.mt_debug_prof(mt.h, None, 1)
 b.apply_async()
 mt.sync()
 print("kernel ms", mt.last_kernel_ms(), "hbm", mt.last_hbm_docs(), "peaks", mt.last_paged_peaks())
+if hasattr(mt.lib, "mt_last_zamboni"):
+    print("zamboni", mt.last_zamboni())
 mt.lib.mt_debug_prof(mt.h, _native.ptr(out), 0)
 # paged documents reuse slots 2, 4, 5 for pg_zamboni internals (scour_range, locate, heap pop)
 names = ["split_seg", "boundary", "scour|pg_scour", "pack", "zamboni|pg_locate", "text_gc|pg_heap_pop", "op_insert", "op_range", "obs_prefix",
@@ -46,6 +48,6 @@ for i, n in enumerate(names):
 events = {16: "zamboni heap pops", 17: "  pops of a gone id (0)", 18: "  pops switching the window",
           19: "  pops whose segment is gone", 20: "  pops of a scoured block (skip)", 21: "  scours",
           22: "  level-1 packs after a scour", 23: "window flushes writing slots", 24: "op window switches",
-          25: "page splits"}
+          25: "page splits", 37: "  scours done in place (page in HBM)", 38: "    of those: nothing to store"}
 for k, n in events.items():
-    print(f"{n:34s} per op {out[64 + k] / ops:8.4f}")
+    print(f"{n:38s} per op {out[64 + k] / ops:8.4f}")

@@ -468,10 +468,13 @@ class MergeTreeBatch:
 
     def last_zamboni(self):
         """Zamboni's scours of the last batch / generation outside the staged page: done in place
-        on the page in HBM, or through the window after all (mt_last_zamboni)."""
+        on the page in HBM, or through the window after all (mt_last_zamboni); in_place_packs:
+        those of in_place that repacked the page's leaf blocks as well (mt_last_zamboni_packs)."""
         out = np.zeros(2, dtype=np.uint32)
         self._check(self.lib.mt_last_zamboni(self.h, _native.ptr(out)), "mt_last_zamboni")
-        return {"in_place": int(out[0]), "fallback": int(out[1])}
+        packs = np.zeros(1, dtype=np.uint32)
+        self._check(self.lib.mt_last_zamboni_packs(self.h, _native.ptr(packs)), "mt_last_zamboni_packs")
+        return {"in_place": int(out[0]), "fallback": int(out[1]), "in_place_packs": int(packs[0])}
 
     def last_grown(self):
         """The last batch's growth step (mt_last_grown): documents moved to larger paged

@@ -948,6 +948,18 @@ TD void blk_split_up(DocT<T> &d, int l, int b) {
     }
 }
 
+// pack's new entries for `total` children (:1414-1446): k = total / 4 clamped to 1..7 entries,
+// the first `extra` of them one child larger than `base`.  The window's pack, the level-1 packs
+// and the paged in-place pack (mt_paged.h pg_pack_inplace) all size their entries here.
+struct PackSplit {
+    int k, base, extra;
+};
+__device__ __forceinline__ PackSplit pack_split(int total) {
+    int k = total / MT_HALF;
+    if (k > MT_MAXN - 1) k = MT_MAXN - 1;
+    if (k < 1) k = 1;
+    return PackSplit{k, total / k, total % k};
+}
 // Replace entries [b0, b0 + nold) of level l with k entries sized base (+1 for the first
 // `extra`), as pack :1414-1446 does; new level-0 blocks have needsScour undefined.
 TD void blk_replace(DocT<T> &d, int l, int b0, int nold, int k, int base, int extra) {
@@ -2228,11 +2240,9 @@ TD void pack(DocT<T> &d, int l, int b) {
         } else {
             for (int cb = c0; cb < c0 + nch; cb++) total += cntr(d, l, cb);
         }
-        int k = total / MT_HALF;
-        if (k > MT_MAXN - 1) k = MT_MAXN - 1;
-        if (k < 1) k = 1;
-        const int base = total / k, extra = total % k;
-        blk_replace(d, l, c0, nch, k, base, extra);
+        const PackSplit ps = pack_split(total);
+        const int k = ps.k;
+        blk_replace(d, l, c0, nch, k, ps.base, ps.extra);
         if (d.status) return;
         if (lane() == 0) lvl(d, l + 1)[P] = (uint8_t)k;
         wsync<T>();
@@ -2259,10 +2269,9 @@ TD void pack_counts(DocT<T> &d, int l, int b, int &top_l, int &top_b) {
         const int nch = cntr(d, l + 1, P);
         int total = 0;
         for (int cb = c0; cb < c0 + nch; cb++) total += cntr(d, l, cb);
-        int k = total / MT_HALF;
-        if (k > MT_MAXN - 1) k = MT_MAXN - 1;
-        if (k < 1) k = 1;
-        blk_replace(d, l, c0, nch, k, total / k, total % k);
+        const PackSplit ps = pack_split(total);
+        const int k = ps.k;
+        blk_replace(d, l, c0, nch, k, ps.base, ps.extra);
         if (d.status) return;
         if (lane() == 0) lvl(d, l + 1)[P] = (uint8_t)k;
         wsync<T>();

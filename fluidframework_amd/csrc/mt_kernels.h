@@ -478,11 +478,13 @@ __device__ __forceinline__ void pg_peaks(const DevState &st, PagedDoc<T> &pd, in
         atomicMax(st.stats + 9, (uint32_t)pk_ut);
         atomicMax(st.stats + 10, (uint32_t)pk_heap);
         atomicMax(st.stats + 11, (uint32_t)ns);
-        // zamboni's scours outside the window: in place / through the window (mt_last_zamboni)
+        // zamboni's scours outside the window: in place / through the window (mt_last_zamboni),
+        // in-place scours that repacked their page (mt_last_zamboni_packs)
         if constexpr (pg_zinplace<T>()) {
-            const uint32_t zi = pg_zcount(pd)[0], zf = pg_zcount(pd)[1];
+            const uint32_t zi = pg_zcount(pd)[0], zf = pg_zcount(pd)[1], zp = pg_zcount(pd)[2];
             if (zi) atomicAdd(st.stats + 16, zi);
             if (zf) atomicAdd(st.stats + 17, zf);
+            if (zp) atomicAdd(st.stats + 18, zp);
         }
     }
 }

@@ -44,7 +44,7 @@
 template <class T> struct PagedDoc {
     DocT<T> w;    // window: one page staged in LDS (first member: see pdoc)
     DocT<T> up;   // levels >= 1 of the tree (level 1 = pages, counted in leaf blocks)
-    LDS_AS PageMeta *meta;    // [PP] by page id (T::kHM: null -- gmeta instead); two counters
+    LDS_AS PageMeta *meta;    // [PP] by page id (T::kHM: null -- gmeta instead); three counters
                               // follow it (pg_zcount)
     GLB_AS PageMeta *gmeta;   // T::kHM: the page metadata in HBM, where it lives for the launch
                               // (observer length, leaf-block counts, needsScour flags)
@@ -141,8 +141,8 @@ static __host__ __device__ inline PagedLayout paged_layout(int PP, int PH, int U
     o = (o + 7u) & ~7u;
     L.offUO = o; o += packed ? 8u * MT_PK_MASKS + MT_PK_MASKS / 8 : ((((uint32_t)ob * UT) + 7u) & ~7u);
     L.offHeap = o; o += 8u * (PH + 1);
-    // (+ 8: the document's in-place / window scour counts, pg_zcount)
-    L.offMeta = o; o += hm ? 0u : (uint32_t)sizeof(PageMeta) * PP + 8u;
+    // (+ 12: the document's in-place / window scour and in-place pack counts, pg_zcount)
+    L.offMeta = o; o += hm ? 0u : (uint32_t)sizeof(PageMeta) * PP + 12u;
     L.offUpage = o; o += packed ? 0u : (2u * UT + 3u) & ~3u;
     L.offCob = o; o += hm ? 8u * (uint32_t)((PP + 63) / 64) + 4u * 64 : 4u * PP;   // cob + cdl + sob, or pvl
     L.offWscr = o; o += 64u * 4;
@@ -1313,10 +1313,8 @@ TD void pg_pack1_impl(PagedDoc<T> &pd, int pos) {
         TB += cntr(up, 1, c0 + j);
         TS += uni(pm_nseg(pd, up.dir[c0 + j]));
     }
-    int k = TB / MT_HALF;
-    if (k > MT_MAXN - 1) k = MT_MAXN - 1;
-    if (k < 1) k = 1;
-    const int base = TB / k, extra = TB % k;
+    const PackSplit ps = pack_split(TB);
+    const int k = ps.k, base = ps.base, extra = ps.extra;
     if (nbr(up, 1) + k > pd.PP) {   // the new pages are taken before the old ones are freed
         pg_fail_cap(w, 7);
         return;
@@ -1474,7 +1472,8 @@ TD void pg_pack1_impl(PagedDoc<T> &pd, int pos) {
 // arena compaction -- is detected before anything is stored, and the window path runs on the
 // page exactly as HBM holds it.
 // The document's counts of zamboni's scours outside the window: [0] done in place, [1] through
-// the window after all (mt_last_zamboni).  In LDS behind the page metadata: two more uniform
+// the window after all (mt_last_zamboni), [2] those of [0] that repacked their page
+// (pg_pack_inplace, mt_last_zamboni_packs).  In LDS behind the page metadata: two more uniform
 // registers through the op loop cost P_C3 32 spilled VGPRs (tools/regs.sh).
 TD LDS_AS uint32_t *pg_zcount(PagedDoc<T> &pd) { return (LDS_AS uint32_t *)(pd.meta + pd.PP); }
 template <class T> constexpr bool pg_zinplace() {
@@ -1484,6 +1483,142 @@ template <class T> constexpr bool pg_zinplace() {
     return !T::kLog && !T::kHM && !T::kLive;
 #endif
 }
+// In-place pack.  A scour that leaves its leaf block under MT_HALF segments makes the window
+// path run scour_range(block), pack(w, 0, b) -- a second scour over every leaf block of the
+// page, then the regrouping of its leaf blocks -- and pg_win_sync.  A page is at most one wave
+// of rows, so both scours run on the rows pg_scour_inplace holds (lane i = slot i), and the
+// regrouping is arithmetic on PageMeta (-DMT_NO_ZPACK compiles the path out: same-tree A/B).
+//   pass one: the plan of block q (pl, the caller's).  Its survivors go to the block's front
+//     and the tail left by a cross-lane push (ds_permute); a merge keeper travels with its
+//     merged length and the trailing-newline flag of its group's last member -- all a plan
+//     reads of a merged row -- so that
+//   pass two is planned before any text moves: every row of the page, block starts from the
+//     nibble counts after pass one.  (The two passes differ: with settled A, removed R, settled
+//     B, pass one unlinks R and B's predecessor is R; pass two sees A before B and joins them.)
+//   Fallbacks to the window path, all decided here, before rows, metadata, the level-1 count,
+//     arena text, text_top or the counters are written: a join longer than MT_GRAN in pass two
+//     (pass one's is the caller's), merges of both passes that may not fit the arena without a
+//     compaction, and a page left with fewer than MT_HALF leaf blocks below a level-2 parent
+//     (pg_pack1 repacks its sibling pages).
+//   Then pass one's text merges run on the rows as loaded and the keepers' offset and flags
+//   follow their rows; pass two's merges run on the moved rows; survivors are stored from the
+//   first changed slot on at their rank, overlap masks fetched only for rows that change slot
+//   (every load before any store); the leaf blocks take pack's sizes (pack_split) with
+//   needsScour undefined, and the level-1 count of the page's directory position follows.
+// The observer length, the uid map, the heap, the unsettled table and the window are untouched,
+// as after an in-place scour.
+template <class T> constexpr bool pg_zpack() {
+#ifdef MT_NO_ZPACK
+    return false;
+#else
+    return pg_zinplace<T>();
+#endif
+}
+__device__ __forceinline__ int lane_push(int v, int dst) { return __builtin_amdgcn_ds_permute(dst << 2, v); }
+// a, b: page pg's rows (lane i = slot i, zero past the page); pl: the plan of its leaf block q
+// (rows bstart .. bstart + count), which leaves fewer than MT_HALF survivors after a removal.
+// true: the window path has to run (nothing was written); false: done.
+TD bool pg_pack_inplace(PagedDoc<T> &pd, int pg, v4i a, v4u b, const ScourPlan &pl, uint32_t bc, int q, int bstart) {
+    DocT<T> &w = pd.w;
+    const int k = lane();
+    const int n = uni(pm_nseg(pd, pg)), nb = uni(pm_nblk(pd, pg));
+    const int cnt = pm_bc_of(bc, q);
+    const int keep = __popcll(pl.m_surv);
+    const int n1 = n - (cnt - keep);   // (< 64: pass one removed a row)
+    if (nb > 8) return true;
+    const bool in = k >= bstart && k < bstart + cnt;
+    const u64 below = (1ull << k) - 1ull;
+    const ScourGroups g1 = scour_groups(a, in, pl.m_join, pl.m_surv);
+    // pass one's result, as far as a plan reads it, in the slots pass one leaves the rows in;
+    // lanes that send nothing (unlinked, joined) push to lane 63, which holds no row afterwards
+    v4i a1 = a;
+    v4u b1 = b;
+    if (g1.m_grp) {
+        const uint32_t lastw = (uint32_t)__shfl((int)b.w, g1.gend & (MT_WAVE - 1), MT_WAVE);
+        if ((g1.m_grp >> k) & 1ull) {
+            a1.x = g1.glen;
+            b1.w = lastw & (SEGF_NL_KNOWN | SEGF_NL);
+        }
+    }
+    const int d1 = k < bstart ? k
+                   : !in      ? k - (cnt - keep)
+                   : ((pl.m_surv >> k) & 1ull) ? bstart + __popcll(pl.m_surv & below) : MT_WAVE - 1;
+    a1 = v4i{lane_push(a1.x, d1), lane_push(a1.y, d1), lane_push(a1.z, d1), lane_push(a1.w, d1)};
+    b1 = v4u{(uint32_t)lane_push((int)b1.x, d1), (uint32_t)lane_push((int)b1.y, d1),
+             (uint32_t)lane_push((int)b1.z, d1), (uint32_t)lane_push((int)b1.w, d1)};
+    const int src1 = lane_push(k, d1);   // the slot this lane's row came from
+    const bool in2 = k < n1;
+    int start2 = 0;
+    {
+        int st = 0;
+        for (int j = 0; j < nb; j++) {
+            if (k >= st) start2 = st;
+            st += j == q ? keep : pm_bc_of(bc, j);
+        }
+    }
+    bool nl2;
+    const ScourPlan p2 = scour_plan(w, a1, b1, in2, false, start2, nl2);
+    if (p2.big) return true;
+    const int total = __popcll(p2.m_surv);
+    const PackSplit ps = pack_split(total);
+    if (ps.k < MT_HALF && pd.up.depth > 2) return true;   // pg_pack1 follows: the window path's
+    const ScourGroups g2 = scour_groups(a1, in2, p2.m_join, p2.m_surv);
+    if ((g1.m_grp | g2.m_grp) && w.text_top + g1.totc + g2.totc > w.T_cap) return true;
+    int pos = -1;
+    if (ps.k != nb) {
+        pos = pg_pos(pd, pg);
+        if (pos < 0) return true;
+    }
+    PG_CNT(21)
+    PG_CNT(37)
+    PG_CNT(39)
+    if (k == 0) {
+        pg_zcount(pd)[0]++;
+        pg_zcount(pd)[2]++;
+    }
+    if (g1.m_grp) {
+        gsync_rd();
+        scour_merge(w, a, b, in, g1);
+        const uint32_t x1 = (uint32_t)lane_push((int)b.x, d1), w1 = (uint32_t)lane_push((int)b.w, d1);
+        if (in2 && ((g1.m_grp >> src1) & 1ull)) {
+            b1.x = x1;
+            b1.w = w1;
+        }
+    }
+    if (g2.m_grp) {
+        gsync_rd();
+        scour_merge(w, a1, b1, in2, g2);
+    }
+    {
+        // the first slot either pass changes (pass one changes some: it removed a row)
+        const u64 chg1 = g1.m_grp | ((((1ull << cnt) - 1ull) << bstart) & ~pl.m_surv);
+        const u64 chg2 = g2.m_grp | (((1ull << n1) - 1ull) & ~p2.m_surv);
+        int first = __ffsll((long long)chg1) - 1;
+        if (chg2) first = min(first, __ffsll((long long)chg2) - 1);
+        const int dst = __popcll(p2.m_surv & below);
+        const bool st = in2 && ((p2.m_surv >> k) & 1ull) && k >= first;
+        const bool mv = st && dst != src1;
+        u64 o = 0;
+        if (mv) o = pd.gO[(size_t)pg * MT_PG_SLOTS + src1];
+        asm volatile("" : "+v"(o));   // (every lane's load before any lane's store)
+        if (st) {
+            pd.gA[(size_t)pg * MT_PG_SLOTS + dst] = a1;
+            pd.gB[(size_t)pg * MT_PG_SLOTS + dst] = b1;
+        }
+        if (mv) pd.gO[(size_t)pg * MT_PG_SLOTS + dst] = o;
+    }
+    if (k == 0) {
+        uint32_t nbc = 0;
+        for (int j = 0; j < ps.k; j++) nbc |= (uint32_t)(ps.base + (j < ps.extra ? 1 : 0)) << (4 * j);
+        pd.meta[pg].bc = nbc;
+        pd.meta[pg].flg2 = 0;   // needsScour undefined on every new block
+        pm_set_ns(pd, pg, total, ps.k);
+        if (pos >= 0) lvl(pd.up, 1)[pos] = (uint8_t)ps.k;
+    }
+    wsync<T>();
+    return false;
+}
+
 // Scours the leaf block of page pg (!= pd.cur, nseg > 0) that holds segment uid.  true: the
 // window path has to run (nothing was written); false: done, or nothing to do.
 TD bool pg_scour_inplace(PagedDoc<T> &pd, int pg, uint32_t uid) {
@@ -1527,8 +1662,11 @@ TD bool pg_scour_inplace(PagedDoc<T> &pd, int pg, uint32_t uid) {
     bool nl_res;
     const ScourPlan pl = scour_plan(w, a, b, in, false, bstart, nl_res);
     const int keep = __popcll(pl.m_surv);
-    // the serial per-block plan, or a pack of the page's leaf blocks: the window path's
-    if (pl.big || (keep < cnt && keep < MT_HALF)) return true;
+    if (pl.big) return true;   // the serial per-block plan: the window path's
+    if (keep < cnt && keep < MT_HALF) {   // pack regroups the page's leaf blocks
+        if constexpr (pg_zpack<T>()) return pg_pack_inplace(pd, pg, a, b, pl, bc, q, bstart);
+        return true;
+    }
     const ScourGroups g = scour_groups(a, in, pl.m_join, pl.m_surv);
     if (g.m_grp && w.text_top + g.totc > w.T_cap) return true;   // the merges need a compaction
     PG_CNT(21)
@@ -2560,7 +2698,7 @@ TD void pg_setup(PagedDoc<T> &pd, const DevState &st, int doc, LDS_AS uint8_t *s
     pd.zpv = 0;
     pd.press = 0;
     if constexpr (!T::kHM) {
-        if (lane() == 0) pg_zcount(pd)[0] = pg_zcount(pd)[1] = 0;
+        if (lane() == 0) pg_zcount(pd)[0] = pg_zcount(pd)[1] = pg_zcount(pd)[2] = 0;
     }
     pd.ovf_top = MT_OVF_HDR;
     pd.ovf_last = 0;

@@ -246,6 +246,11 @@ int mt_last_paged_peaks(mt_handle *h, uint32_t *out);
    leaf blocks or a text compaction was needed)}.  Tiers with a delta log or with their page
    metadata in HBM always move the window and count neither. */
 int mt_last_zamboni(mt_handle *h, uint32_t *out);
+/* Of the scours mt_last_zamboni counts as done in place: out[1] = those that left their leaf
+   block under four segments and repacked the page's leaf blocks in place as well (both of
+   pack's scours and its regrouping on the page in HBM; a pack that goes on to level 1, a join
+   above the append granularity or a text compaction still takes the window). */
+int mt_last_zamboni_packs(mt_handle *h, uint32_t *out);
 
 /* Growth step of the most recent batch (mt_sync runs it; see mt_options: the paged
    capacities are where documents start, not a limit): out[6] = {documents handed to it,

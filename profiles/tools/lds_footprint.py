@@ -15,7 +15,7 @@ def pcnt_bytes(B):   # mt_engine.h pcnt_off(B, MT_LV): levels 0-1 B each, level 
 def paged_lds(PP, UT, PH, ob=4, hm=0, gen_words=0):
     o = 16 * MT_PG_SLOTS * 2 + ob * MT_PG_SLOTS
     o += 16 * UT + ((ob * UT + 7) & ~7)
-    o += 8 * (PH + 1) + (0 if hm else META * PP) + ((2 * UT + 3) & ~3)
+    o += 8 * (PH + 1) + (0 if hm else META * PP + 12) + ((2 * UT + 3) & ~3)
     o += 8 * ((PP + 63) // 64) + 256 if hm else 4 * PP   # chunk sums + obs cache, or pvl (r5)
     o += 64 * 4 + MT_LV * 4 * 2 + 4 * gen_words + 2 * PP + 2 * 16 + MT_LV * 16 + 16
     o += pcnt_bytes(PP) - PP

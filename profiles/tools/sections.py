@@ -48,6 +48,7 @@ for i, n in enumerate(names):
 events = {16: "zamboni heap pops", 17: "  pops of a gone id (0)", 18: "  pops switching the window",
           19: "  pops whose segment is gone", 20: "  pops of a scoured block (skip)", 21: "  scours",
           22: "  level-1 packs after a scour", 23: "window flushes writing slots", 24: "op window switches",
-          25: "page splits", 37: "  scours done in place (page in HBM)", 38: "    of those: nothing to store"}
+          25: "page splits", 37: "  scours done in place (page in HBM)", 38: "    of those: nothing to store",
+          39: "    of those: page repacked in place"}
 for k, n in events.items():
     print(f"{n:38s} per op {out[64 + k] / ops:8.4f}")

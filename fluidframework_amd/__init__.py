@@ -684,11 +684,96 @@ class MergeTreeBatch:
                 out.append((s, l, [(int(recs[r + 1 + 2 * j]), int(recs[r + 2 + 2 * j])) for j in range(n)]))
         return out
 
+    # bulk / ranged property runs (mt_get_prop_runs_bulk): get_prop_runs clipped to [start, end)
+    # for many documents in one counting pass and one gather on the device
+    def get_prop_runs_raw(self, docs=None, start=None, end=None):
+        """(run_off, word_off, runs[R, 3], records): query q's rows (position, length, record) are
+        runs[run_off[q]:run_off[q + 1]]; a row's record [count, (key, value) x count] starts at
+        records[word_off[q] + record] (record 0xFFFFFFFF: no properties).  Queries as in
+        get_texts."""
+        n, docs, start, end, _ = self._text_queries(docs, start, end, 0)
+        run_off = np.zeros(n + 1, dtype=np.int64)
+        word_off = np.zeros(n + 1, dtype=np.int64)
+        args = (self.h, n, _native.ptr(docs), _native.ptr(start), _native.ptr(end), _native.ptr(run_off),
+                _native.ptr(word_off))
+        self._check(self.lib.mt_get_prop_runs_bulk(*args, None, 0, None, 0), "mt_get_prop_runs_bulk")
+        nr, nw = int(run_off[n]), int(word_off[n])
+        runs = np.zeros((max(nr, 1), 3), dtype=np.uint32)
+        recs = np.zeros(max(nw, 1), dtype=np.uint32)
+        self._check(self.lib.mt_get_prop_runs_bulk(*args, _native.ptr(runs), nr, _native.ptr(recs), nw),
+                    "mt_get_prop_runs_bulk")
+        return run_off, word_off, runs[:nr], recs[:nw]
+
+    @staticmethod
+    def _prop_run_lists(run_off, word_off, runs, recs):
+        rows, words = runs.tolist(), recs.tolist()
+        out = []
+        for q in range(len(run_off) - 1):
+            w0 = int(word_off[q])
+            res = []
+            for s, l, r in rows[int(run_off[q]): int(run_off[q + 1])]:
+                if r == 0xFFFFFFFF:
+                    res.append((s, l, None))
+                else:
+                    r += w0
+                    res.append((s, l, [(words[r + 1 + 2 * j], words[r + 2 + 2 * j]) for j in range(words[r])]))
+            out.append(res)
+        return out
+
+    def get_prop_runs_bulk(self, docs=None, start=None, end=None):
+        """get_prop_runs-shaped lists (position, length, pairs | None), one per query
+        (doc, start, end): every document when docs is None, whole documents when start / end
+        are None (an end of -1 or None: the document's length).  start and end are clamped into
+        [0, length]; positions stay document coordinates."""
+        return self._prop_run_lists(*self.get_prop_runs_raw(docs, start, end))
+
+    def get_properties_at_positions(self, docs, positions):
+        """The property pairs (or None) at each (doc, position): one bulk call with ranges of
+        width 1.  A position outside [0, length) answers None."""
+        pos = np.asarray(positions, dtype=np.int64).reshape(-1)
+        ok = (pos >= 0) & (pos < 0x7FFFFFFF)   # (position + 1 stays an int32)
+        start = np.where(ok, pos, 0).astype(np.int32)
+        end = np.where(ok, pos + 1, 0).astype(np.int32)
+        docs = np.broadcast_to(np.asarray(docs, dtype=np.uint32), pos.shape)
+        return [r[0][2] if r else None for r in self.get_prop_runs_bulk(docs, start, end)]
+
+    def get_prop_runs_device(self, docs=None, start=None, end=None, out=None):
+        """get_prop_runs_raw with the results left on the handle's device: (run_off, word_off,
+        runs, records) torch tensors (int64 [n + 1] twice, int32 [R, 3] and int32 [W] holding the
+        uint32 words).  out: (runs, records) int32 tensors on that device to fill (at least the
+        results' sizes; runs of shape [rows, 3]); the results are then their leading slices.
+        (torch is imported before the first handle is created, as for get_texts_device.)"""
+        import torch
+        n, docs, start, end, _ = self._text_queries(docs, start, end, 0)
+        dev = torch.device("cuda", self.device)
+        run_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        word_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        args = (self.h, n, _native.ptr(docs), _native.ptr(start), _native.ptr(end),
+                ctypes.c_void_p(run_off.data_ptr()), ctypes.c_void_p(word_off.data_ptr()))
+        if out is None:
+            self._check(self.lib.mt_get_prop_runs_bulk_device(*args, None, 0, None, 0), "mt_get_prop_runs_bulk_device")
+            runs = torch.empty((max(int(run_off[n]), 1), 3), dtype=torch.int32, device=dev)
+            recs = torch.empty(max(int(word_off[n]), 1), dtype=torch.int32, device=dev)
+        else:
+            runs, recs = out
+            for t in (runs, recs):
+                if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+                    raise ValueError("get_prop_runs_device: out holds contiguous int32 tensors on the handle's device")
+            if runs.dim() != 2 or runs.shape[1] != 3 or recs.dim() != 1:
+                raise ValueError("get_prop_runs_device: out is (runs [rows, 3], records [words])")
+        self._check(self.lib.mt_get_prop_runs_bulk_device(*args, ctypes.c_void_p(runs.data_ptr()), runs.shape[0],
+                                                          ctypes.c_void_p(recs.data_ptr()), recs.numel()),
+                    "mt_get_prop_runs_bulk_device")
+        return run_off, word_off, runs[: int(run_off[n])], recs[: int(word_off[n])]
+
+    def last_props_ms(self):
+        """Device time (ms) of the last bulk property-run call's counting pass and gather."""
+        out = np.zeros(2, dtype=np.float32)
+        self._check(self.lib.mt_last_props_ms(self.h, _native.ptr(out)), "mt_last_props_ms")
+        return float(out[0]), float(out[1])
+
     def get_properties_at_position(self, doc, pos):
-        for s, l, p in self.get_prop_runs(doc):
-            if s <= pos < s + l:
-                return p
-        return None
+        return self.get_properties_at_positions([doc], [pos])[0]
 
     def debug_raw(self, doc):
         """Raw segment records (n x 8 u32: segA, segB) and the 32-word document header."""

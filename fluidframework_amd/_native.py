@@ -99,6 +99,9 @@ SIGNATURES = [
     ("mt_get_texts_device", _I, [_P, _U32, _P, _P, _P, ctypes.c_uint16, _P, _P, _U64]),
     ("mt_last_text_ms", _I, [_P, _P]),
     ("mt_get_prop_runs", _I, [_P, _U32, _P, _U32, _P, _P, _U32, _P]),
+    ("mt_get_prop_runs_bulk", _I, [_P, _U32, _P, _P, _P, _P, _P, _P, _U64, _P, _U64]),
+    ("mt_get_prop_runs_bulk_device", _I, [_P, _U32, _P, _P, _P, _P, _P, _P, _U64, _P, _U64]),
+    ("mt_last_props_ms", _I, [_P, _P]),
     ("mt_get_segments", _I, [_P, _U32, _P, _U32, _P, _P, _U32, _P]),
     ("mt_get_segment_props", _I, [_P, _U32, _U32, _P, _U32, _P]),
     ("mt_get_all_segment_props", _I, [_P, _U32, _P, ctypes.c_uint64, _P]),

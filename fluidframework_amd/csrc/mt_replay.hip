@@ -633,6 +633,161 @@ __global__ void __launch_bounds__(MT_WAVE) k_text_gather(DevState st, int nq, co
     if (!kPerSeg && carry && lane() == 0) o[done - 1] = (uint16_t)carry_v;   // the tail
 }
 
+// ---------------------------------------------------------------- bulk property-run read-out
+// mt_get_prop_runs clipped to [start, end) for many (doc, start, end) queries: the walk of
+// k_text_count (markers count one position).  A lane whose segment has a position inside the
+// range contributes; it heads a run when the nearest contributing segment before it -- a lower
+// lane of the chunk, else the wave-uniform carry across chunks and pages -- does not hold the
+// same property set (mt_get_prop_runs' `same`: equal handles, or two records equal word for
+// word).  Removed and clipped-away segments contribute nothing, so they neither break a run
+// nor start one.
+#define MT_PROPS_NONE 0xFFFFFFFFu   // carry: no contributing segment yet; row: no properties
+struct PropsLane {
+    int units;       // positions of the lane's segment inside the range
+    uint32_t eh;     // its record handle (0: none; a handle >= P or a count > MT_KMAX reads as 0)
+    int cnt;         // keys of that record
+    bool head;       // the segment starts a run
+};
+__device__ __forceinline__ PropsLane props_chunk(const v4i *A, const v4u *Bv, int i, int n, const TextQuery &Q,
+                                                 const uint32_t *pr, uint32_t P, int &pos, uint32_t &carry) {
+    PropsLane L;
+    int src;
+    L.units = text_clip(A, Bv, i, n, Q.s, Q.e, 1, pos, src);
+    const uint32_t ph = i < n ? Bv[i].y : 0u;
+    const uint32_t hi = ph < P ? ph : 0u;
+    const uint32_t c = pr[(size_t)hi * MT_PREC];
+    const bool ok = (hi != 0u) & (c <= (uint32_t)MT_KMAX);
+    L.eh = ok ? hi : 0u;
+    L.cnt = ok ? (int)c : 0;
+    const bool con = L.units > 0;
+    const u64 contrib = ballot(con);
+    const u64 below = contrib & ((1ull << lane()) - 1ull);
+    const int pl = below ? 63 - __clzll((long long)below) : lane();
+    const uint32_t got = (uint32_t)__shfl((int)L.eh, pl, MT_WAVE);
+    const uint32_t prev = below ? got : carry;
+    // both handles are validated ones (or the carry's "none"), so every record read is in bounds;
+    // the words are loaded unconditionally and masked (no short-circuit)
+    const bool cmp = con & (prev != MT_PROPS_NONE) & (prev != L.eh) & (prev != 0u) & (L.eh != 0u);
+    bool eq = prev == L.eh;
+    if (ballot(cmp)) {
+        const uint32_t *x = pr + (size_t)(cmp ? prev : 0u) * MT_PREC, *y = pr + (size_t)(cmp ? L.eh : 0u) * MT_PREC;
+        const uint32_t cx = x[0];
+        uint32_t diff = cx ^ y[0];
+#pragma unroll
+        for (uint32_t k = 0; k < 2 * MT_KMAX; k++) {
+            const uint32_t xv = x[1 + k], yv = y[1 + k];
+            diff |= (k < 2u * cx ? 0xFFFFFFFFu : 0u) & (xv ^ yv);
+        }
+        eq = eq | (cmp & (diff == 0u));
+    }
+    L.head = con & !eq;
+    if (contrib) carry = (uint32_t)bcast((int)L.eh, 63 - __clzll((long long)contrib));
+    return L;
+}
+__global__ void __launch_bounds__(MT_WAVE) k_props_count(DevState st, int nq, const uint32_t *docs, const int32_t *start,
+                                                         const int32_t *end, int64_t *n_runs, int64_t *n_words) {
+    const int q = blockIdx.x;
+    if (q >= nq) return;
+    const TextQuery Q = text_query(st, q, docs, start, end);
+    int runs = 0, words = 0;
+    if (Q.s < Q.e) {
+        const DocHdr h = st.hdr[Q.doc];
+        const SegRanges R = seg_ranges(st, Q.doc, h);
+        const PagedBase ar = doc_paged(st, Q.doc);   // (the arenas of the document's region)
+        const uint32_t P = (uint32_t)ar.P;
+        const uint32_t *pr = ar.props + (size_t)h.props_half * P * MT_PREC;
+        int pos = 0;
+        uint32_t carry = MT_PROPS_NONE;
+        for (int r = 0; r < R.count() && pos < Q.e; r++) {
+            const v4i *A;
+            const v4u *Bv;
+            int n;
+            R.get(r, A, Bv, n);
+            for (int base = 0; base < n && pos < Q.e; base += MT_WAVE) {
+                const PropsLane L = props_chunk(A, Bv, base + lane(), n, Q, pr, P, pos, carry);
+                runs += __popcll(ballot(L.head));
+                words += (L.head & (L.eh != 0u)) ? 1 + 2 * L.cnt : 0;
+            }
+        }
+        words = wave_sum(words);
+    }
+    if (lane() == 0) {
+        n_runs[q] = runs;
+        n_words[q] = words;
+    }
+}
+// Writes query q's rows at runs[3 * run_off[q] ..) and its records at records[word_off[q] ..).
+// A head lane writes its row's position and record offset at its rank (heads before it in the
+// chunk plus the runs done) and copies its record's words (<= 17, a per-lane loop) to the
+// words done plus an exclusive scan of the chunk's word counts.  Visible positions tile the
+// range, so a run's length is the next head's position minus its own: inside a chunk from that
+// head's lane; the chunk's last run stays open in wave-uniform state {row, position} until the
+// next head, or the end of the walk, closes it.  Rows and words are checked against the
+// query's slots, so a failed document's inconsistent rows cannot write outside the result.
+__global__ void __launch_bounds__(MT_WAVE) k_props_gather(DevState st, int nq, const uint32_t *docs,
+                                                          const int32_t *start, const int32_t *end,
+                                                          const int64_t *run_off, const int64_t *word_off,
+                                                          uint32_t *runs, uint32_t *records) {
+    const int q = blockIdx.x;
+    if (q >= nq) return;
+    const TextQuery Q = text_query(st, q, docs, start, end);
+    const int64_t room_r = run_off[q + 1] - run_off[q], room_w = word_off[q + 1] - word_off[q];
+    if (Q.s >= Q.e || room_r <= 0) return;
+    const DocHdr h = st.hdr[Q.doc];
+    const SegRanges R = seg_ranges(st, Q.doc, h);
+    const PagedBase ar = doc_paged(st, Q.doc);
+    const uint32_t P = (uint32_t)ar.P;
+    const uint32_t *pr = ar.props + (size_t)h.props_half * P * MT_PREC;
+    uint32_t *rows = runs + 3 * run_off[q];
+    uint32_t *rec = records + word_off[q];
+    int pos = 0;
+    uint32_t carry = MT_PROPS_NONE;
+    int done = 0;             // positions of the range covered so far
+    int64_t runs_done = 0, words_done = 0;
+    int64_t open_row = -1;    // the run not yet closed, and its position
+    int open_pos = 0;
+    for (int r = 0; r < R.count() && pos < Q.e; r++) {
+        const v4i *A;
+        const v4u *Bv;
+        int n;
+        R.get(r, A, Bv, n);
+        for (int base = 0; base < n && pos < Q.e; base += MT_WAVE) {
+            const PropsLane L = props_chunk(A, Bv, base + lane(), n, Q, pr, P, pos, carry);
+            const u64 hm = ballot(L.head);
+            const int incl = wave_scan_incl(L.units);
+            const int wc = (L.head & (L.eh != 0u)) ? 1 + 2 * L.cnt : 0;
+            const int winc = wave_scan_incl(wc);
+            if (hm) {
+                const int p = Q.s + done + incl - L.units;   // the segment's first position inside the range
+                const int64_t rank = runs_done + __popcll(hm & ((1ull << lane()) - 1ull));
+                const u64 above = hm & ~((2ull << lane()) - 1ull);
+                const int np = __shfl(p, above ? first_lane(above) : lane(), MT_WAVE);
+                const int64_t w0 = words_done + winc - wc;
+                const bool fits = (wc > 0) & (w0 + wc <= room_w);
+                if (L.head && rank < room_r) {
+                    uint32_t *row = rows + 3 * rank;
+                    row[0] = (uint32_t)p;
+                    if (above) row[1] = (uint32_t)(np - p);
+                    row[2] = fits ? (uint32_t)w0 : MT_PROPS_NONE;
+                }
+                if (L.head && fits) {
+                    const uint32_t *x = pr + (size_t)L.eh * MT_PREC;
+                    rec[w0] = (uint32_t)L.cnt;
+                    for (int k = 1; k < wc; k++) rec[w0 + k] = x[k];
+                }
+                const int fp = bcast(p, first_lane(hm)), lp = bcast(p, 63 - __clzll((long long)hm));
+                if (open_row >= 0 && open_row < room_r && lane() == 0) rows[3 * open_row + 1] = (uint32_t)(fp - open_pos);
+                runs_done += __popcll(hm);
+                open_row = runs_done - 1;
+                open_pos = lp;
+            }
+            done += bcast(incl, 63);
+            words_done += bcast(winc, 63);
+        }
+    }
+    if (open_row >= 0 && open_row < room_r && lane() == 0) rows[3 * open_row + 1] = (uint32_t)(Q.s + done - open_pos);
+}
+
 // ============================================================================ host side
 // ---------------------------------------------------------------- live-client reconnect
 // regeneratePendingOp for the oldest pending segment group of one document (one wave):
@@ -782,6 +937,8 @@ struct mt_handle {
     bool load_timed = false;   // ev_load / ev_load1 bracket the last snapshot load's kernels
     hipEvent_t ev_txt[4] = {nullptr, nullptr, nullptr, nullptr};   // mt_get_texts: around its counting pass, around its gather
     int txt_timed = 0;         // 1: the counting pass was bracketed, 2: the gather as well
+    hipEvent_t ev_prp[4] = {nullptr, nullptr, nullptr, nullptr};   // mt_get_prop_runs_bulk: the same two brackets
+    int prp_timed = 0;
     // documents per workgroup of the LDS-tier replay (env MT_WPG=2 for two): measured on C2
     // the CU saturates at 16 resident documents (16 -> 18 per CU: 61.8 -> 64.6 ms)
     int wpg = 1;
@@ -1153,6 +1310,8 @@ void mt_destroy(mt_handle *h) {
     if (h->ev_load) hipEventDestroy(h->ev_load);
     if (h->ev_load1) hipEventDestroy(h->ev_load1);
     for (hipEvent_t e : h->ev_txt)
+        if (e) hipEventDestroy(e);
+    for (hipEvent_t e : h->ev_prp)
         if (e) hipEventDestroy(e);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -2871,6 +3030,127 @@ int mt_last_text_ms(mt_handle *h, float *out) {
     out[0] = out[1] = 0.f;
     if (h->txt_timed >= 1) HIPCHK(h, hipEventElapsedTime(&out[0], h->ev_txt[0], h->ev_txt[1]));
     if (h->txt_timed >= 2) HIPCHK(h, hipEventElapsedTime(&out[1], h->ev_txt[2], h->ev_txt[3]));
+    return 0;
+}
+
+// mt_get_prop_runs_bulk / mt_get_prop_runs_bulk_device: get_texts' shape with two counts per
+// query (runs, record words), so two prefix sums and two outputs.
+static int get_prop_runs_bulk(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start,
+                              const int32_t *end, int64_t *run_off, int64_t *word_off, void *runs, uint64_t cap_runs,
+                              void *records, uint64_t cap_words, bool device) {
+    if (!h || n > 0x7FFFFFFFu || !run_off || !word_off) return MT_E_INVALID;
+    if (!docs && n > h->n_docs) return MT_E_INVALID;
+    if (docs)
+        for (uint32_t q = 0; q < n; q++)
+            if (docs[q] >= h->n_docs) return MT_E_INVALID;
+    HIPCHK(h, hipSetDevice(h->device));
+    SETTLE(h);
+    h->prp_timed = 0;
+    if (n == 0) {
+        if (device) {
+            HIPCHK(h, hipMemset(run_off, 0, 8));
+            HIPCHK(h, hipMemset(word_off, 0, 8));
+        } else {
+            run_off[0] = word_off[0] = 0;
+        }
+        return 0;
+    }
+    for (hipEvent_t &e : h->ev_prp)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    // one allocation: [docs | start | end] (n words each, absent ones stay unused), the run and
+    // word counts [n] each, the two offset arrays [n + 1] each
+    DevBuf args, d_runs, d_recs;
+    const size_t words = (size_t)n * 3 + (n & 1);   // (the 8-byte arrays stay aligned)
+    HIPCHK(h, hipMalloc(&args.p, words * 4 + ((size_t)n * 4 + 2) * 8));
+    uint32_t *d_docs = (uint32_t *)args.p;
+    int32_t *d_start = (int32_t *)args.p + n, *d_end = (int32_t *)args.p + 2 * (size_t)n;
+    int64_t *d_nr = (int64_t *)((uint32_t *)args.p + words), *d_nw = d_nr + n;
+    int64_t *d_roff = d_nw + n, *d_woff = d_roff + n + 1;
+    if (docs) HIPCHK(h, hipMemcpy(d_docs, docs, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (start) HIPCHK(h, hipMemcpy(d_start, start, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (end) HIPCHK(h, hipMemcpy(d_end, end, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (!docs) d_docs = nullptr;
+    if (!start) d_start = nullptr;
+    if (!end) d_end = nullptr;
+    HIPCHK(h, hipEventRecord(h->ev_prp[0], h->stream));
+    hipLaunchKernelGGL(k_props_count, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start, d_end,
+                       d_nr, d_nw);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev_prp[1], h->stream));
+    int64_t total_r = 0, total_w = 0;
+    if (device) {
+        d_roff = run_off;
+        d_woff = word_off;
+        hipLaunchKernelGGL(k_text_scan, dim3(1), dim3(1024), 0, h->stream, d_nr, (int)n, d_roff);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(k_text_scan, dim3(1), dim3(1024), 0, h->stream, d_nw, (int)n, d_woff);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(&total_r, d_roff + n, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(&total_w, d_woff + n, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    } else {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(run_off + 1, d_nr, (size_t)n * 8, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(word_off + 1, d_nw, (size_t)n * 8, hipMemcpyDeviceToHost));
+        run_off[0] = word_off[0] = 0;
+        for (uint32_t q = 0; q < n; q++) {
+            run_off[q + 1] += run_off[q];
+            word_off[q + 1] += word_off[q];
+        }
+        total_r = run_off[n];
+        total_w = word_off[n];
+    }
+    h->prp_timed = 1;
+    if (!runs) return 0;   // sizing only
+    if (!records) cap_words = 0;
+    if (cap_runs < (uint64_t)total_r || cap_words < (uint64_t)total_w) {
+        h->err = "mt_get_prop_runs_bulk: the outputs hold " + std::to_string(cap_runs) + " runs and " +
+                 std::to_string(cap_words) + " words, the results need " + std::to_string(total_r) + " runs and " +
+                 std::to_string(total_w) + " words";
+        return MT_E_OVERFLOW;
+    }
+    if (total_r == 0) return 0;
+    uint32_t *g_runs = (uint32_t *)runs, *g_recs = (uint32_t *)records;
+    if (!device) {
+        HIPCHK(h, hipMemcpy(d_roff, run_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(d_woff, word_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMalloc(&d_runs.p, (size_t)total_r * 12));
+        HIPCHK(h, hipMalloc(&d_recs.p, (size_t)std::max<int64_t>(total_w, 1) * 4));
+        g_runs = (uint32_t *)d_runs.p;
+        g_recs = (uint32_t *)d_recs.p;
+    }
+    HIPCHK(h, hipEventRecord(h->ev_prp[2], h->stream));
+    hipLaunchKernelGGL(k_props_gather, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start, d_end,
+                       d_roff, d_woff, g_runs, g_recs);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev_prp[3], h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->prp_timed = 2;
+    if (!device) {
+        HIPCHK(h, hipMemcpy(runs, g_runs, (size_t)total_r * 12, hipMemcpyDeviceToHost));
+        if (total_w) HIPCHK(h, hipMemcpy(records, g_recs, (size_t)total_w * 4, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+int mt_get_prop_runs_bulk(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
+                          int64_t *run_off, int64_t *word_off, uint32_t *runs, uint64_t cap_runs, uint32_t *records,
+                          uint64_t cap_words) {
+    return get_prop_runs_bulk(h, n, docs, start, end, run_off, word_off, runs, cap_runs, records, cap_words, false);
+}
+
+int mt_get_prop_runs_bulk_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start,
+                                 const int32_t *end, void *run_off_dev, void *word_off_dev, void *runs_dev,
+                                 uint64_t cap_runs, void *records_dev, uint64_t cap_words) {
+    return get_prop_runs_bulk(h, n, docs, start, end, (int64_t *)run_off_dev, (int64_t *)word_off_dev, runs_dev,
+                              cap_runs, records_dev, cap_words, true);
+}
+
+int mt_last_props_ms(mt_handle *h, float *out) {
+    if (!h || !out) return MT_E_INVALID;
+    out[0] = out[1] = 0.f;
+    if (h->prp_timed >= 1) HIPCHK(h, hipEventElapsedTime(&out[0], h->ev_prp[0], h->ev_prp[1]));
+    if (h->prp_timed >= 2) HIPCHK(h, hipEventElapsedTime(&out[1], h->ev_prp[2], h->ev_prp[3]));
     return 0;
 }
 

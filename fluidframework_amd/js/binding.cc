@@ -584,6 +584,69 @@ napi_value GetPropRuns(napi_env env, napi_callback_info info) {
     return obj;
 }
 
+// getPropRunsBulk(h, docs|null, start|null, end|null) -> {runOff: Float64Array [n + 1],
+// wordOff: Float64Array [n + 1], runs: Uint32Array (position, length, record) x R, records:
+// Uint32Array}   (mt_get_prop_runs_bulk: getPropRuns clipped to [start, end) for many queries in
+// one counting pass and one gather; arguments as getTexts'.  Query q's rows start at
+// runs[3 * runOff[q]]; a row's record is records[wordOff[q] + record ..], 0xFFFFFFFF: none.)
+napi_value GetPropRunsBulk(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    Handle *hd = get_handle(env, argv[0]);
+    if (!hd) return nullptr;
+    void *ptrs[3] = {nullptr, nullptr, nullptr};
+    size_t lens[3] = {0, 0, 0};
+    const napi_typedarray_type want[3] = {napi_uint32_array, napi_int32_array, napi_int32_array};
+    for (int i = 0; i < 3; i++) {
+        napi_valuetype vt;
+        NAPI_CALL(env, napi_typeof(env, argv[1 + i], &vt));
+        if (vt == napi_null || vt == napi_undefined) continue;
+        napi_typedarray_type t;
+        napi_value ab;
+        size_t off;
+        if (napi_get_typedarray_info(env, argv[1 + i], &t, &lens[i], &ptrs[i], &ab, &off) != napi_ok || t != want[i]) {
+            napi_throw_type_error(env, nullptr, "getPropRunsBulk: docs is a Uint32Array, start and end are Int32Arrays (or null)");
+            return nullptr;
+        }
+        if (!ptrs[i]) ptrs[i] = &lens[i];   // (an empty array: any non-null pointer, never read)
+    }
+    const size_t n = ptrs[0] ? lens[0] : mt_num_docs(hd->h);
+    if ((ptrs[1] && lens[1] != n) || (ptrs[2] && lens[2] != n)) {
+        napi_throw_range_error(env, nullptr, "getPropRunsBulk: start and end hold one entry per query");
+        return nullptr;
+    }
+    std::vector<int64_t> roff(n + 1), woff(n + 1);
+    int rc = mt_get_prop_runs_bulk(hd->h, (uint32_t)n, (const uint32_t *)ptrs[0], (const int32_t *)ptrs[1],
+                                   (const int32_t *)ptrs[2], roff.data(), woff.data(), nullptr, 0, nullptr, 0);
+    if (rc) return throw_rc(env, hd, rc, "mt_get_prop_runs_bulk");
+    const size_t nr = (size_t)roff[n], nw = (size_t)woff[n];
+    void *rd, *wd, *rod, *wod;
+    napi_value rab, wab, roab, woab, ra, wa, roa, woa, obj;
+    NAPI_CALL(env, napi_create_arraybuffer(env, 3 * nr * 4, &rd, &rab));
+    NAPI_CALL(env, napi_create_arraybuffer(env, nw * 4, &wd, &wab));
+    NAPI_CALL(env, napi_create_arraybuffer(env, (n + 1) * 8, &rod, &roab));
+    NAPI_CALL(env, napi_create_arraybuffer(env, (n + 1) * 8, &wod, &woab));
+    uint32_t none = 0;   // (an empty result: any non-null pointer, never written)
+    rc = mt_get_prop_runs_bulk(hd->h, (uint32_t)n, (const uint32_t *)ptrs[0], (const int32_t *)ptrs[1],
+                               (const int32_t *)ptrs[2], roff.data(), woff.data(), nr ? (uint32_t *)rd : &none, nr,
+                               nw ? (uint32_t *)wd : &none, nw);
+    if (rc) return throw_rc(env, hd, rc, "mt_get_prop_runs_bulk");
+    for (size_t q = 0; q <= n; q++) {
+        ((double *)rod)[q] = (double)roff[q];
+        ((double *)wod)[q] = (double)woff[q];
+    }
+    NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, 3 * nr, rab, 0, &ra));
+    NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, nw, wab, 0, &wa));
+    NAPI_CALL(env, napi_create_typedarray(env, napi_float64_array, n + 1, roab, 0, &roa));
+    NAPI_CALL(env, napi_create_typedarray(env, napi_float64_array, n + 1, woab, 0, &woa));
+    NAPI_CALL(env, napi_create_object(env, &obj));
+    NAPI_CALL(env, napi_set_named_property(env, obj, "runOff", roa));
+    NAPI_CALL(env, napi_set_named_property(env, obj, "wordOff", woa));
+    NAPI_CALL(env, napi_set_named_property(env, obj, "runs", ra));
+    NAPI_CALL(env, napi_set_named_property(env, obj, "records", wa));
+    return obj;
+}
+
 // getDeltaLog(h, doc) -> Int32Array (only with deltaLogCapacity > 0; oracle layout)
 napi_value GetDeltaLog(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -830,7 +893,7 @@ napi_value Init(napi_env env, napi_value exports) {
     } fns[] = {{"create", Create},         {"destroy", Destroy},           {"loadInitialText", LoadInitialText},
                  {"startCollaboration", StartCollaboration},
                {"applyOps", ApplyOps},     {"loadSnapshots", LoadSnapshots},     {"status", Status},             {"getLength", GetLength},
-               {"getText", GetText},       {"getTexts", GetTexts},         {"getPropRuns", GetPropRuns},   {"getDeltaLog", GetDeltaLog},
+               {"getText", GetText},       {"getTexts", GetTexts},         {"getPropRuns", GetPropRuns}, {"getPropRunsBulk", GetPropRunsBulk},   {"getDeltaLog", GetDeltaLog},
                {"deltaLogReset", DeltaLogReset},
                {"maintenanceCounts", MaintenanceCounts},
                {"checksums", Checksums},   {"lastKernelMs", LastKernelMs}, {"numDocs", NumDocs},

@@ -299,6 +299,53 @@ class GpuMergeTreeBatch {
         return native.getTexts(this.h, docs === undefined || docs === null ? null : Uint32Array.from(docs), null, null, 0);
     }
 
+    /**
+     * Property runs of many queries (doc, start, end) in one counting pass and one gather
+     * (mt_get_prop_runs_bulk): per query a list of {position, length, props} clipped to
+     * [start, end), in document coordinates; props is undefined for a run without properties.
+     * docs: document indices (repeats allowed), every document when omitted; start / end: one
+     * entry per query, whole documents when omitted (an end below 0: the document's length).
+     */
+    getPropertyRuns(docs, start, end) {
+        this.flush();
+        const nil = (v) => v === undefined || v === null;
+        const r = native.getPropRunsBulk(this.h, nil(docs) ? null : Uint32Array.from(docs),
+            nil(start) ? null : Int32Array.from(start), nil(end) ? null : Int32Array.from(end));
+        const out = [];
+        for (let q = 0; q + 1 < r.runOff.length; q++) {
+            const rows = [];
+            for (let i = r.runOff[q]; i < r.runOff[q + 1]; i++) {
+                rows.push({ position: r.runs[3 * i], length: r.runs[3 * i + 1],
+                    props: this._recordProps(r.records, r.wordOff[q], r.runs[3 * i + 2]) });
+            }
+            out.push(rows);
+        }
+        return out;
+    }
+
+    /**
+     * Client.getPropertiesAtPosition for many (doc, position) pairs in one call: ranges of
+     * width 1.  A position outside [0, length) answers undefined, as does one without properties.
+     */
+    getPropertiesAtPositions(docs, positions) {
+        const ok = (p) => Number.isInteger(p) && p >= 0 && p < 0x7FFFFFFF;
+        const pos = Array.from(positions);
+        const runs = this.getPropertyRuns(docs, pos.map((p) => (ok(p) ? p : 0)), pos.map((p) => (ok(p) ? p + 1 : 0)));
+        return runs.map((r) => (r.length ? r[0].props : undefined));
+    }
+
+    _recordProps(records, base, rec) {
+        if (rec === 0xFFFFFFFF) { return undefined; }
+        const at = base + rec, n = records[at];
+        const pairs = [];
+        for (let j = 0; j < n; j++) {
+            pairs.push([this.interner.keyName(records[at + 1 + 2 * j]), this.interner.value(records[at + 2 + 2 * j])]);
+        }
+        const props = {};
+        for (const [k, v] of jsKeyOrder(pairs)) { props[k] = v; }
+        return props;
+    }
+
     lastKernelMs() { return native.lastKernelMs(this.h); }
 
     dispose() { native.destroy(this.h); }
@@ -515,26 +562,20 @@ class GpuClient {
         };
     }
 
-    /** Client.getPropertiesAtPosition (client.ts:1011-1025). */
+    /** Client.getPropertiesAtPosition (client.ts:1011-1025): one width-1 query on the device. */
     getPropertiesAtPosition(pos) {
         this._sync();
-        const { runs, records } = native.getPropRuns(this.batch.h, this.doc);
-        for (let i = 0; i < runs.length; i += 3) {
-            const start = runs[i], len = runs[i + 1], rec = runs[i + 2];
-            if (pos >= start && pos < start + len) {
-                if (rec === 0xFFFFFFFF) { return undefined; }
-                const n = records[rec];
-                const pairs = [];
-                for (let j = 0; j < n; j++) {
-                    pairs.push([this.batch.interner.keyName(records[rec + 1 + 2 * j]),
-                        this.batch.interner.value(records[rec + 2 + 2 * j])]);
-                }
-                const props = {};
-                for (const [k, v] of jsKeyOrder(pairs)) { props[k] = v; }
-                return props;
-            }
-        }
-        return undefined;
+        return this.batch.getPropertiesAtPositions([this.doc], [pos])[0];
+    }
+
+    /**
+     * The document's property runs inside [start, end) as [{position, length, props}] (whole
+     * document when omitted; clamped into [0, length]); props is undefined without properties.
+     */
+    getPropertyRuns(start, end) {
+        this._sync();
+        return this.batch.getPropertyRuns([this.doc], [start === undefined ? 0 : start],
+            [end === undefined ? -1 : end])[0];
     }
 
     /**

@@ -331,6 +331,40 @@ int mt_last_text_ms(mt_handle *h, float *out /* [2] */);
 int mt_get_prop_runs(mt_handle *h, uint32_t doc, uint32_t *runs, uint32_t cap_runs,
                      uint32_t *n_runs, uint32_t *records, uint32_t cap_words,
                      uint32_t *n_words);
+/* mt_get_prop_runs clipped to [start, end) for n queries (doc, start, end) in one counting pass
+   and one gather on the device.  Queries, arguments and errors are mt_get_texts': docs NULL:
+   documents 0..n-1 (n <= n_docs); start / end NULL: whole documents; end[q] < 0: the document's
+   length; both ends are clamped into [0, length] and start >= end gives zero runs; a
+   doc >= n_docs is MT_E_INVALID; the same document may appear in many queries; the call settles
+   the handle first; failed documents answer from the state they stopped in.
+   - Visible segments (removed seq MT_RSEQ_NONE) are taken in document order; a marker is one
+     position with its own property set.  A segment extends the current run when its record
+     handle equals the run's, or both are non-zero and the records are equal word for word
+     (count and (key, value) words in order); handle 0 (no properties) extends only a run of
+     handle 0.  Removed segments do not break a run.  A segment with no position inside
+     [start, end) contributes nothing and starts no run; the first contributing segment of a
+     query always starts one.
+   - Query q's rows are three uint32 at runs + 3 * run_off[q], back to back: position (the run's
+     first position inside the range, document coordinates), length (positions inside the
+     range), record (the offset of the run's record relative to word_off[q]; 0xFFFFFFFF: no
+     properties).  Each run with a record has its own copy [count, (key, value) x count] at
+     records + word_off[q] + record (no deduplication).
+   - run_off[n + 1] and word_off[n + 1] always receive the prefix sums.  runs NULL: sizing only.
+     cap_runs < run_off[n] or cap_words < word_off[n]: MT_E_OVERFLOW, nothing written to runs or
+     records; mt_last_error names both needs. */
+int mt_get_prop_runs_bulk(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start,
+                          const int32_t *end, int64_t *run_off /* [n+1] */, int64_t *word_off /* [n+1] */,
+                          uint32_t *runs, uint64_t cap_runs, uint32_t *records, uint64_t cap_words);
+/* The same with run_off, word_off (int64[n + 1]), runs (uint32[3 * cap_runs]) and records
+   (uint32[cap_words]) in device memory on the handle's device; docs / start / end stay host
+   arrays.  The prefix sums are taken on the device; the call returns once the results are
+   written. */
+int mt_get_prop_runs_bulk_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start,
+                                 const int32_t *end, void *run_off_dev, void *word_off_dev,
+                                 void *runs_dev, uint64_t cap_runs, void *records_dev, uint64_t cap_words);
+/* Device time of the most recent mt_get_prop_runs_bulk(_device) call's two kernels (HIP events):
+   out[0] the counting pass, out[1] the gather (0 after a sizing call). */
+int mt_last_props_ms(mt_handle *h, float *out /* [2]: counting pass, gather */);
 /* Diagnostic: segment rows of 8 int32 (len, seq, client, rseq, rclient, n_overlap,
    marker refType or -1, has_props) in document order, and the leaf-block partition. */
 int mt_get_segments(mt_handle *h, uint32_t doc, int32_t *rows, uint32_t cap_rows,

@@ -337,6 +337,24 @@ TD int pg_obs_start(PagedDoc<T> &pd) {
     }
     return wave_sum(s);
 }
+// The document's observer length as the metadata holds it (the window's page as of its last
+// sync; T::kHM: the chunk sums pg_obs_start reads).  An estimate of the live text for
+// pg_arena_room, not an exact figure: markers count one unit and hold no text.
+TD int pg_obs_total(PagedDoc<T> &pd) {
+    const int np = nbr(pd.up, 1);
+    int s = 0;
+    if constexpr (T::kHM) {
+        gsync_rd();
+        const int nc = (np + MT_WAVE - 1) >> 6;
+        for (int base = 0; base < nc; base += MT_WAVE) s += base + lane() < nc ? pd.cob[base + lane()] : 0;
+    } else {
+        for (int base = 0; base < np; base += MT_WAVE) {
+            const int q = base + lane();
+            s += q < np ? pm_obs(pd, pd.up.dir[q]) : 0;
+        }
+    }
+    return wave_sum(s);
+}
 // Chunk observer lengths from the pages (after the directory changed: page split, pack at
 // level 1, load, conversion): one wave sum per chunk of 64 positions.
 TD void pg_cob_rebuild(PagedDoc<T> &pd) {
@@ -2461,12 +2479,17 @@ TD int pg_ovf_need_counted(PagedDoc<T> &pd, const mt_op_rec &op) {
 // compaction left an arena nearly full (press); a growing launch compacts here, between
 // messages, and hands the document to the
 // growth step (cause 4 text / 5 records / 9 uid map, kept in HDR_DIAG with status 0) when the
-// live text / records / segments then leave less than 1/8 of it free (and at least 4096 text
-// units / 128 records / 64 ids, for a message's merges; 11: the overflow overlap
-// sets, never reclaimed, half of it) -- so a message never fails half applied, and a document
-// whose live data fits is compacted, not moved.  The
-// bound covers an insert's own text and one range step's records (props_ensure(d, MT_WAVE));
-// a zamboni merge's copy is served by the half kept free.
+// live records / segments then leave less than 1/8 of it free (and at least 128 records /
+// 64 ids; 11: the overflow overlap sets, never reclaimed, half of it), or when the live text
+// with the insert's own does not fit twice below the 1/8 (at least 4096 units) kept free -- a
+// document whose live data fits is compacted, not moved.  The bound covers an insert's own
+// text and one range step's records (props_ensure(d, MT_WAVE)) exactly.  For a zamboni merge's
+// copy, which no row's length bounds (TextSegment.append keeps appending to a keeper of any
+// length), it is a heuristic: between compactions the live text is estimated from the observer
+// length (pg_obs_total), so a message can still run out of text in the middle
+// (MT_DOC_CAPACITY) where that estimate is short; it is far rarer than with the arena judged
+// only when full.  An arena of 4096 units or fewer has no room below the slack at all: the
+// document is handed over at its first messages until the arena has been doubled past 8192.
 TD bool pg_arena_room(PagedDoc<T> &pd, const mt_op_rec &op, const PagedCaps &pc) {
     DocT<T> &w = pd.w;
     const int nt = op.kind == MT_OP_INSERT && !(op.flags & MT_F_MARKER) ? max(op.pos2, 0) : 0;
@@ -2494,8 +2517,32 @@ TD bool pg_arena_room(PagedDoc<T> &pd, const mt_op_rec &op, const PagedCaps &pc)
     // a tight launch compacts inside the message (text_ensure) and hands the document on once
     // a compaction leaves an arena nearly full (press); the uid map is renumbered at the next
     // tier's message start
-    if (pc.tight) return u_ok && !pd.press;
-    if (t_ok && p_ok && u_ok) return true;
+    if (pc.tight) {
+        // (press is judged at a compaction, and the first one comes when the arena is full: of
+        // a document whose text is nearly all live it reclaims nothing and the message would
+        // fail in the middle.  In the arena's last eighth the observer length, an estimate of
+        // the live text, tells whether a compaction can leave that eighth free; if not, the
+        // document goes on)
+        const long long full = 7ll * w.T_cap;
+        if (8ll * ((long long)w.text_top + nt) > full && 8ll * ((long long)pg_obs_total(pd) + nt) > full)
+            return false;
+        return u_ok && !pd.press;
+    }
+    // A zamboni merge copies its whole group to the arena's top (scour_merge: a keeper of any
+    // length moves with what it absorbs) inside the message, where nothing can be handed over
+    // any more, and a compaction there reclaims only what is dead.  A growing launch therefore
+    // looks for room before the arena is full: at 7/8 it compacts, and it hands the document
+    // on unless the text left (the longest copy there can be, with the insert's own) fits twice.
+    // Compactions inside messages leave the arena's top at the live text, so between them the
+    // same is asked of the observer length, an estimate of it, once the top no longer fits twice.
+    const long long t_lim = (long long)w.T_cap - max(w.T_cap / 8, 4096);
+    bool t_room = t_ok;
+    if constexpr (T::kMayGrow) {
+        t_room = (long long)w.text_top + nt <= t_lim;
+        if (t_room && 2ll * ((long long)w.text_top + nt) > t_lim)
+            t_room = 2ll * ((long long)pg_obs_total(pd) + nt) <= t_lim;
+    }
+    if (t_room && p_ok && u_ok) return true;
     if constexpr (T::kMayGrow) {
         {
             if (!u_ok) {   // (the renumbering pg_apply_op would do, done here; cause 9)
@@ -2506,10 +2553,10 @@ TD bool pg_arena_room(PagedDoc<T> &pd, const mt_op_rec &op, const PagedCaps &pc)
                     return false;
                 }
             }
-            if (!t_ok) {
+            if (!t_room) {
                 paged_text_compact(w);
                 if (w.status) return true;   // (failed: the loop stops)
-                if (w.text_top + nt > w.T_cap - max(w.T_cap / 8, 4096)) {   // (slack: merges' copies)
+                if (2ll * ((long long)w.text_top + nt) > t_lim) {
                     w.cap_cause = 4;
                     return false;
                 }

@@ -8,7 +8,14 @@ outputs (text, length, property runs, leaf-block partition, segment table, every
 callback).  The fixtures are data, not reference source.
 
     python3 tests/golden/make_golden.py [--snapshots | --farm | --errors | --rich | --events | --live |
-                                         --readouts-xl | --only name,name]
+                                         --readouts-xl | --only name,name |
+                                         --zamboni [name,name]]
+
+--zamboni makes the zamboni stream fixtures (ref_zam_long, ref_zam_settle, ref_zam_marks,
+ref_zam_shrink, ref_zam_comb; all of them, or the names listed) from the configs and message
+logs of tests/zam_streams.py; ref_zam_shrink reads the committed ref_c3.  Their files carry no
+timestamp, so a regeneration reproduces them byte for byte.  Run tests/golden/make_maint.py
+afterwards: ref_maint.json holds their maintenance-event counts too.
 """
 import gzip
 import json
@@ -326,8 +333,72 @@ def make_live_fixtures(only=None):
         print(name, ndocs, "docs", sum(len(d["events"]) for d in data["docs"]), "events")
 
 
+# Zamboni streams (--zamboni): what scour, merge and pack meet off the C3 distribution.  The
+# configs and the hand-built logs are tests/zam_streams.py's (shared with the tests); the
+# outputs are the reference's (harness "gen" and "replay").  Written without a timestamp:
+# regenerating reproduces the files byte for byte.
+def _dump_fixed(name, data):
+    with open(os.path.join(HERE, name + ".json.gz"), "wb") as raw:
+        with gzip.GzipFile(filename="", mode="wb", fileobj=raw, mtime=0) as fh:
+            fh.write(json.dumps(data, separators=(",", ":")).encode())
+
+
+def _harness(mode, inp, *args):
+    with tempfile.TemporaryDirectory() as td:
+        ip, op = os.path.join(td, "in.json"), os.path.join(td, "out.json")
+        json.dump(inp, open(ip, "w"))
+        subprocess.check_call(["node", os.path.join(REPO, "oracle", "ref_harness.mjs"), mode, ip] +
+                              [str(a) for a in args] + [op])
+        return json.load(open(op))
+
+
+def make_zamboni_fixtures(only=None):
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import zam_streams as zs
+    for name, cfg in zs.RANDOM_CONFIGS.items():
+        if only and name not in only:
+            continue
+        data = _harness("gen", cfg, 0, zs.RANDOM_DOCS)
+        for d in data["docs"]:
+            d["out"].pop("tree", None)
+            d.pop("ref_ns", None)
+        _dump_fixed(name, data)
+        print(name, [zs.row_stats(d["out"]) for d in data["docs"]])
+    if not only or "ref_zam_shrink" in only:
+        with gzip.open(os.path.join(HERE, zs.SHRINK_FROM + ".json.gz"), "rt") as fh:
+            src = json.load(fh)
+        docs = [zs.shrink_doc(d, src["config"]["writers"], i) for i, d in enumerate(src["docs"][:zs.SHRINK_DOCS])]
+        for d, o in zip(docs, _harness("replay", {"docs": docs})["docs"]):
+            d["out"] = o["out"]
+            d["out"].pop("tree", None)
+        _dump_fixed("ref_zam_shrink", dict(config=dict(src["config"], zam="shrink", source=zs.SHRINK_FROM,
+                                                       source_msgs=len(src["docs"][0]["msgs"])), docs=docs))
+        print("ref_zam_shrink", [zs.row_stats(d["out"]) for d in docs])
+    if not only or "ref_zam_comb" in only:
+        docs = []
+        for case in zs.COMB_CASES:
+            d, cuts = zs.comb_doc(case)
+            logs = [dict(d, msgs=d["msgs"][:n]) for n in cuts]
+            outs = [o["out"] for o in _harness("replay", {"docs": logs})["docs"]]
+            for o in outs:
+                o.pop("tree", None)
+            d["out"] = outs[-1]
+            # a checkpoint's delta records are the first n_deltas of the final replay's
+            d["checkpoints"] = []
+            for n, o in zip(cuts, outs):
+                assert o["deltas"] == d["out"]["deltas"][:len(o["deltas"])]
+                d["checkpoints"].append([n, dict(o, deltas=len(o["deltas"]))])
+            docs.append(d)
+            print("ref_zam_comb", case, zs.row_stats(d["out"]))
+        _dump_fixed("ref_zam_comb", dict(config={"ext": True, "zam": "comb"}, docs=docs))
+
+
 def main():
     subprocess.check_call([sys.executable, os.path.join(REPO, "oracle", "build_ref.py")])
+    if "--zamboni" in sys.argv[1:]:
+        i = sys.argv.index("--zamboni")
+        make_zamboni_fixtures(set(sys.argv[i + 1].split(",")) if len(sys.argv) > i + 1 else None)
+        return
     if "--live" in sys.argv[1:]:
         only = sys.argv[sys.argv.index("--live") + 1].split(",") if len(sys.argv) > sys.argv.index("--live") + 1 else None
         make_live_fixtures(only)

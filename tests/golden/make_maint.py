@@ -15,7 +15,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 FIXTURES = ["ref_small", "ref_c2", "ref_c3", "ref_c4", "ref_ext", "ref_ext_long", "ref_farm", "ref_c3_full",
-            "ref_c4_full"]
+            "ref_c4_full", "ref_zam_long", "ref_zam_settle", "ref_zam_marks", "ref_zam_shrink", "ref_zam_comb"]
 
 
 def main():

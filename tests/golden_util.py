@@ -10,12 +10,16 @@ import numpy as np
 from fluidframework_amd.snapshot import SnapshotBatch, decode_chunks
 from fluidframework_amd.wire import Batch, Interner, compact_msgs_to_dicts, from_fixture
 
+# zamboni streams off the C3 distribution (tests/zam_streams.py, make_golden.py --zamboni): rows
+# over MT_GRAN, streams that settle at once, markers and newlines on pages, a document that
+# empties and regrows, hand-built combs whose far pages are scoured block by block
+ZAM_FIXTURES = ["ref_zam_long", "ref_zam_settle", "ref_zam_marks", "ref_zam_shrink", "ref_zam_comb"]
 MAINT_FIXTURES = ["ref_small", "ref_c2", "ref_c3", "ref_c4", "ref_ext", "ref_ext_long", "ref_farm", "ref_c3_full",
-                  "ref_c4_full"]
+                  "ref_c4_full"] + ZAM_FIXTURES
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 INT_MIN = -2 ** 31
 ALL_FIXTURES = ["ref_small", "ref_c2", "ref_c3", "ref_c4", "ref_ext", "ref_ext_long", "ref_farm", "ref_c3_full",
-                "ref_c4_full", "ref_combine", "ref_wide"]
+                "ref_c4_full", "ref_combine", "ref_wide"] + ZAM_FIXTURES
 # the configs' full stream lengths (10k messages per document)
 FULL_FIXTURES = ["ref_c3_full", "ref_c4_full"]
 # long-lived documents (30k messages)
@@ -93,6 +97,34 @@ def expected(doc, interner):
                     flat += [interner.key(k), _sid(interner.val(from_fixture(v)))]
     return dict(text=out["text"], length=out["length"], leaves=out["leaves"], segs=segs,
                 seg_props=seg_props, deltas=flat)
+
+
+def checkpoints(doc):
+    """[(n_msgs, reference outputs after the first n_msgs messages)] of a document that records
+    them (ref_zam_comb); a checkpoint stores the count of its delta records, which are the first
+    of the final replay's."""
+    return [(n, dict(out, deltas=doc["out"]["deltas"][:out["deltas"]])) for n, out in doc.get("checkpoints", [])]
+
+
+def batches_to(a, docs, cuts):
+    """The op records of `docs` (a: encode_docs over exactly these documents) cut into batches:
+    batch j holds, per document d, the records of its messages cuts[d][j-1] .. cuts[d][j]
+    (message counts, ascending, as many per document, the last one its whole log).  Records are
+    taken by their message's sequence number; text and property arenas are shared."""
+    off, seq = a["doc_off"], a["ops"]["seq"]
+    bounds = []
+    for d, doc in enumerate(docs):
+        c = list(cuts[d])
+        assert c == sorted(set(c)) and c[0] > 0 and c[-1] == len(doc["msgs"]) and len(c) == len(cuts[0])
+        rec_seq = seq[off[d]:off[d + 1]]
+        bounds.append([0] + [int(np.searchsorted(rec_seq, doc["msgs"][n - 1][1], side="right")) for n in c])
+        assert bounds[-1][-1] == len(rec_seq)
+    out = []
+    for j in range(len(cuts[0])):
+        idx = [np.arange(off[d] + b[j], off[d] + b[j + 1]) for d, b in enumerate(bounds)]
+        doc_off = np.concatenate([[0], np.cumsum([len(i) for i in idx])]).astype(np.int64)
+        out.append(dict(a, ops=a["ops"][np.concatenate(idx)], doc_off=doc_off))
+    return out
 
 
 def expected_live(doc, interner):

@@ -195,7 +195,7 @@ def _replay(name, tier, **kw):
 # ---------------------------------------------------------------- 1. whole documents, every tier
 @pytest.mark.gpu
 @pytest.mark.parametrize("tier", list(TIERS))
-@pytest.mark.parametrize("name", ["ref_small", "ref_ext", "ref_c3", "ref_combine"])
+@pytest.mark.parametrize("name", ["ref_small", "ref_ext", "ref_c3", "ref_combine", "ref_zam_long"])
 def test_bulk_props_whole_documents_match_reference(name, tier):
     """All documents in one call: (A) and (B); 24 fixed-seed ranges per document; for the
     fixtures with markers, ranges that begin at, end at, and hold only a marker; ref_small (no

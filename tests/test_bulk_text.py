@@ -136,7 +136,7 @@ def _replay(name, tier, **kw):
 # ---------------------------------------------------------------- 1. whole documents, every tier
 @pytest.mark.gpu
 @pytest.mark.parametrize("tier", list(TIERS))
-@pytest.mark.parametrize("name", ["ref_small", "ref_ext", "ref_c3"])
+@pytest.mark.parametrize("name", ["ref_small", "ref_ext", "ref_c3", "ref_zam_long"])
 def test_bulk_text_whole_documents_match_reference(name, tier):
     """get_texts() equals the reference's text of every document and get_text(d); with the " "
     placeholder it is the position-space string (ref_ext: markers); a fixed-seed set of ranges

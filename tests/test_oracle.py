@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import golden_util as gu
+import zam_streams as zs
 
 
 @pytest.mark.parametrize("name", gu.ALL_FIXTURES + gu.LONG_FIXTURES + gu.WIDE_FIXTURES + gu.XL_FIXTURES)
@@ -17,6 +18,56 @@ def test_oracle_matches_reference(oracle_lib, name):
         od.apply_all(a["ops"], a["text"], a["props"])
         errs = gu.compare_oracle(od.outputs(), gu.expected(doc, interner))
         assert not errs, f"{name} doc {doc['doc']}: {errs}"
+
+
+def test_oracle_matches_reference_at_comb_checkpoints(oracle_lib):
+    """ref_zam_comb applied in batches that end at the recorded checkpoints (after the prefix,
+    after every 100 trigger messages): the restatement equals the reference's replay of the
+    truncated log at each of them, delta records included."""
+    fx = gu.load("ref_zam_comb")
+    interner = gu.interner_for(fx)
+    for doc in fx["docs"]:
+        a = gu.encode_docs(fx, interner, [doc])
+        od = oracle_lib.OracleDoc.new(a["seed"][: a["seed_off"][1]])
+        cps = gu.checkpoints(doc)
+        assert len(cps) == 5 and cps[-1][0] == len(doc["msgs"])
+        for (n, out), part in zip(cps, gu.batches_to(a, [doc], [[n for n, _ in cps]])):
+            od.apply_all(part["ops"], a["text"], a["props"])
+            errs = gu.compare_oracle(od.outputs(), gu.expected(dict(doc, out=out), interner))
+            assert not errs, f"{doc['doc']} after {n} messages: {errs}"
+
+
+def test_zamboni_fixtures_keep_what_they_are_for():
+    """Conditions on the committed zamboni fixtures (tests/zam_streams.py), so that a regenerated
+    one cannot quietly lose the rows, blocks and events it exists for."""
+    maint = {name: gu.maint_counts(name) for name in gu.ZAM_FIXTURES}
+    for doc in gu.load("ref_zam_long")["docs"]:
+        st = zs.row_stats(doc["out"])
+        assert st["over_gran"] >= 10 and st["over_wave"] >= 100 and st["blocks"] >= 80, (doc["doc"], st)
+    fx = gu.load("ref_zam_settle")
+    for doc, (_, append, _) in zip(fx["docs"], maint["ref_zam_settle"]):
+        st = zs.row_stats(doc["out"])
+        assert st["blocks"] >= 150 and st["over_gran"] >= 5 and append >= fx["config"]["ops"], (doc["doc"], st, append)
+    for doc in gu.load("ref_zam_marks")["docs"]:
+        st = zs.row_stats(doc["out"])
+        assert st["rows"] >= 400 and st["markers"] >= 60 and st["nl_rows"] >= 60, (doc["doc"], st)
+    fx, src = gu.load("ref_zam_shrink"), gu.load(zs.SHRINK_FROM)
+    assert len(fx["docs"]) == zs.SHRINK_DOCS
+    for doc, base in zip(fx["docs"], src["docs"]):
+        n = len(base["msgs"])
+        assert doc["msgs"][:n] == base["msgs"] and len(doc["msgs"]) == n + zs.SHRINK_TAIL
+        ln = zs.tail_lengths(base["out"]["length"], doc["msgs"][n:])
+        assert 0 in ln and max(ln[ln.index(0):]) >= zs.SHRINK_HIGH and ln[-1] == doc["out"]["length"], doc["doc"]
+        assert len(base["out"]["leaves"]) >= 190 and len(doc["out"]["leaves"]) <= 25, doc["doc"]
+    fx = gu.load("ref_zam_comb")
+    assert [d["doc"] for d in fx["docs"]] == list(zs.COMB_CASES)
+    for doc, (_, append, unlink) in zip(fx["docs"], maint["ref_zam_comb"]):
+        st = zs.row_stats(doc["out"])
+        assert (st["rows"], st["blocks"], append, unlink) == zs.COMB_FINAL[doc["doc"]], (doc["doc"], st, append, unlink)
+        built, cuts = zs.comb_doc(doc["doc"])
+        assert built["msgs"] == doc["msgs"] and cuts == [n for n, _ in doc["checkpoints"]]
+    assert zs.row_stats(fx["docs"][0]["out"])["longest"] == 3399
+    assert zs.row_stats(fx["docs"][1]["out"])["longest"] == 24399
 
 
 def test_oracle_error_model_matches_reference(oracle_lib):

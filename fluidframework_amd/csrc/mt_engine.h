@@ -1953,80 +1953,95 @@ __device__ __forceinline__ ScourGroups scour_groups(const v4i &a, bool in, u64 m
     }
     return g;
 }
-// Text merges group by group, on rows in registers (as the arena holds them now: after any
-// compaction); the room for g.totc units is the caller's to ensure.  A keeper copied to the
-// arena top reserves slack after its text so that later appends land in place
+// The text merge of one group, for scour_merge (rows in registers) and scour_range (the
+// window's rows); only the serial scour_block keeps a form of its own: keeper kk (its row bk, its
+// length ak, wave-uniform) takes the members kk+1 .. ge behind it (bm: this lane's row, ax its
+// length; L the inclusive lengths, gk the merged length, from scour_groups).  Rows are as the
+// arena holds them now, after any compaction; the room is the caller's to ensure.  Contiguous
+// texts stay where they are.  Otherwise the members go into the keeper's slack, or behind a
+// keeper that ends at the arena's top, or the keeper moves to the top with them; a keeper
+// written at the top reserves slack after its text so that later appends land in place
 // (TextSegment.append :70-85 is a string concatenation; this keeps it amortised O(1)).
-// The keepers' lanes (g.m_grp) leave with their merged length, offset and flags in a / b.
-TD void scour_merge(DocT<T> &d, v4i &a, v4u &b, bool in, const ScourGroups &g) {
+// Returns the keeper's merged length, text offset and flags word for the caller to store.
+struct ScourKeeper {
+    int len;
+    uint32_t off, w;
+};
+TD ScourKeeper scour_group(DocT<T> &d, const v4u &bk, int ak, const v4u &bm, int ax, bool in, int L, int ge, int gk,
+                           int kk) {
     const int k = lane();
+    const uint32_t kslack = bk.w >> SEGF_SLACK_SHIFT;
+    // members kk+1..ge: contiguity of their text after the keeper's
+    const bool mem = k > kk && k <= ge;
+    const int Lm = L - (in ? ax : 0);         // exclusive prefix of lengths
+    const int Lk = bcast(L, kk) - ak;         // keeper's exclusive prefix
+    const int rel = Lm - Lk;                  // member's offset inside the merged text
+    const bool contig_lane = !mem || (int)bm.x == (int)bk.x + rel;
+    const bool contig = !ballot(!contig_lane);
+    const int add = gk - ak;
+    const uint32_t lastw = (uint32_t)bcast((int)bm.w, ge);
+    // the merged text is newline-free when the keeper's and every member's are
+    const uint32_t nonl = (bk.w & SEGF_NONL) && !ballot(mem && !(bm.w & SEGF_NONL)) ? SEGF_NONL : 0u;
+    uint32_t newoff = bk.x, newslack = lastw >> SEGF_SLACK_SHIFT;
+    if (!contig) {
+        int dst;
+        bool move_keeper = false;
+        if ((uint32_t)add <= kslack) {                       // append into the slack
+            dst = (int)bk.x + ak;
+            newslack = kslack - (uint32_t)add;
+        } else if ((int)bk.x + ak == d.text_top) {          // keeper ends at the top
+            dst = d.text_top;
+            newslack = (uint32_t)text_slack(gk);
+            d.text_top += add + (int)newslack;
+        } else {                                            // move keeper + appends
+            newoff = (uint32_t)d.text_top;
+            dst = d.text_top + ak;
+            move_keeper = true;
+            newslack = (uint32_t)text_slack(gk);
+            d.text_top += gk + (int)newslack;
+        }
+        GLB_AS uint16_t *tb = text_base(d, d.text_half);
+        // gather: unit t of the merged text (t < gk); units < ak come from the keeper
+        const int t0 = move_keeper ? 0 : ak;
+        for (int base = t0; base < gk; base += MT_WAVE) {
+            const int t = base + lane();
+            int src = 0;
+            if (t < ak) {
+                src = (int)bk.x + t;
+            } else {
+                // member whose exclusive prefix (relative) is <= t: scan members
+                for (int j = kk + 1; j <= ge; j++) {
+                    const int rj = bcast(Lm, j) - Lk;
+                    if (t >= rj) src = bcast((int)bm.x, j) + (t - rj);
+                }
+            }
+            uint16_t ch = 0;
+            if (t < gk) ch = tb[src];
+            if (t < gk) tb[(move_keeper ? (int)newoff : dst - ak) + t] = ch;
+        }
+    }
+    return ScourKeeper{gk, newoff, (lastw & (SEGF_NL_KNOWN | SEGF_NL)) | nonl | (newslack << SEGF_SLACK_SHIFT)};
+}
+// The merges of a plan on rows in registers (the paged in-place routes, mt_paged.h); the room
+// for g.totc units is the caller's to ensure.  The keepers' lanes (g.m_grp) leave with their
+// merged length, offset and flags in a / b.
+TD void scour_merge(DocT<T> &d, v4i &a, v4u &b, bool in, const ScourGroups &g) {
     const v4i a0 = a;
     const v4u bm = b;
-    const int L = g.L;
     for (u64 q = g.m_grp; q; q &= q - 1) {
         const int kk = first_lane(q);
-        const int gk = bcast(g.glen, kk);
-        const int ge = bcast(g.gend, kk);
         const v4u bk = v4u{(uint32_t)bcast((int)bm.x, kk), (uint32_t)bcast((int)bm.y, kk),
                            (uint32_t)bcast((int)bm.z, kk), (uint32_t)bcast((int)bm.w, kk)};
-        const int ak = bcast(a0.x, kk);
-        const uint32_t kslack = bk.w >> SEGF_SLACK_SHIFT;
-        // members kk+1..ge: contiguity of their text after the keeper's
-        const bool mem = k > kk && k <= ge;
-        const int Lm = L - (in ? a0.x : 0);       // exclusive prefix of lengths
-        const int Lk = bcast(L, kk) - ak;         // keeper's exclusive prefix
-        const int rel = Lm - Lk;                  // member's offset inside the merged text
-        const bool contig_lane = !mem || (int)bm.x == (int)bk.x + rel;
-        const bool contig = !ballot(!contig_lane);
-        const int add = gk - ak;
-        const uint32_t lastw = (uint32_t)bcast((int)bm.w, ge);
-        // the merged text is newline-free when the keeper's and every member's are
-        const uint32_t nonl = (bk.w & SEGF_NONL) && !ballot(mem && !(bm.w & SEGF_NONL)) ? SEGF_NONL : 0u;
-        uint32_t newoff = bk.x, newslack = lastw >> SEGF_SLACK_SHIFT;
-        if (!contig) {
-            int dst;
-            bool move_keeper = false;
-            if ((uint32_t)add <= kslack) {                       // append into the slack
-                dst = (int)bk.x + ak;
-                newslack = kslack - (uint32_t)add;
-            } else if ((int)bk.x + ak == d.text_top) {          // keeper ends at the top
-                dst = d.text_top;
-                newslack = (uint32_t)text_slack(gk);
-                d.text_top += add + (int)newslack;
-            } else {                                            // move keeper + appends
-                newoff = (uint32_t)d.text_top;
-                dst = d.text_top + ak;
-                move_keeper = true;
-                newslack = (uint32_t)text_slack(gk);
-                d.text_top += gk + (int)newslack;
-            }
-            GLB_AS uint16_t *tb = text_base(d, d.text_half);
-            // gather: unit t of the merged text (t < gk); units < ak come from the keeper
-            const int t0 = move_keeper ? 0 : ak;
-            for (int base = t0; base < gk; base += MT_WAVE) {
-                const int t = base + lane();
-                int src = 0;
-                if (t < ak) {
-                    src = (int)bk.x + t;
-                } else {
-                    // member whose exclusive prefix (relative) is <= t: scan members
-                    for (int j = kk + 1; j <= ge; j++) {
-                        const int rj = bcast(Lm, j) - Lk;
-                        if (t >= rj) src = bcast((int)bm.x, j) + (t - rj);
-                    }
-                }
-                uint16_t ch = 0;
-                if (t < gk) ch = tb[src];
-                if (t < gk) tb[(move_keeper ? (int)newoff : dst - ak) + t] = ch;
-            }
-        }
-        if (k == kk) {
-            a.x = gk;
-            b.x = newoff;
-            b.w = (lastw & (SEGF_NL_KNOWN | SEGF_NL)) | nonl | (newslack << SEGF_SLACK_SHIFT);
+        const ScourKeeper r =
+            scour_group(d, bk, bcast(a0.x, kk), bm, a0.x, in, g.L, bcast(g.gend, kk), bcast(g.glen, kk), kk);
+        if (lane() == kk) {
+            a.x = r.len;
+            b.x = r.off;
+            b.w = r.w;
         }
     }
 }
+
 
 // scourNode :1322-1398 applied, in order, to the consecutive leaf blocks [b0, b0 + nbk)
 // whose segments start at index s -- one block for zamboniSegments, every child of the
@@ -2092,74 +2107,21 @@ TD int scour_range(DocT<T> &d, int s, int b0, int nbk) {
         mark_dirty(d, s);
         if (!text_ensure(d, g.totc)) return tot;
         gsync_rd();
-        // text merges group by group, on the window's rows (fresh: text_ensure may have
-        // compacted); scour_merge is the same arithmetic on rows in registers -- a fix to
-        // slack, contiguity or move-keeper goes into both.  (Calling scour_merge here, with the
-        // rows reloaded after text_ensure and the keepers written back, was built: holding the
-        // rows across the groups took P_C3 from 8 to 22 spilled VGPRs, tools/regs.sh.)
-        const int L = g.L;
+        // group by group; the rows are re-read per group (text_ensure may have compacted), so
+        // no row stays in registers across the groups
         for (u64 q = g.m_grp; q; q &= q - 1) {
             const int kk = first_lane(q);
             const int gk = bcast(g.glen, kk);
             const int ge = bcast(g.gend, kk);
             const v4u bk = uni4(d.Bv[s + kk]);
             const int ak = uni(d.A[s + kk].x);
-            const uint32_t kslack = bk.w >> SEGF_SLACK_SHIFT;
-            // members kk+1..ge: contiguity of their text after the keeper's
-            const bool mem = k > kk && k <= ge;
-            const v4u bm = d.Bv[mem ? s + k : s];   // fresh offsets after a possible gc
-            const int Lm = L - (in ? a.x : 0);        // exclusive prefix of lengths
-            const int Lk = bcast(L, kk) - ak;         // keeper's exclusive prefix
-            const int rel = Lm - Lk;                  // member's offset inside the merged text
-            const bool contig_lane = !mem || (int)bm.x == (int)bk.x + rel;
-            const bool contig = !ballot(!contig_lane);
-            const int add = gk - ak;
-            const uint32_t lastw = (uint32_t)bcast((int)bm.w, ge);
-            // the merged text is newline-free when the keeper's and every member's are
-            const uint32_t nonl = (bk.w & SEGF_NONL) && !ballot(mem && !(bm.w & SEGF_NONL)) ? SEGF_NONL : 0u;
-            uint32_t newoff = bk.x, newslack = lastw >> SEGF_SLACK_SHIFT;
-            if (!contig) {
-                int dst;
-                bool move_keeper = false;
-                if ((uint32_t)add <= kslack) {                       // append into the slack
-                    dst = (int)bk.x + ak;
-                    newslack = kslack - (uint32_t)add;
-                } else if ((int)bk.x + ak == d.text_top) {          // keeper ends at the top
-                    dst = d.text_top;
-                    newslack = (uint32_t)text_slack(gk);
-                    d.text_top += add + (int)newslack;
-                } else {                                            // move keeper + appends
-                    newoff = (uint32_t)d.text_top;
-                    dst = d.text_top + ak;
-                    move_keeper = true;
-                    newslack = (uint32_t)text_slack(gk);
-                    d.text_top += gk + (int)newslack;
-                }
-                GLB_AS uint16_t *tb = text_base(d, d.text_half);
-                // gather: unit t of the merged text (t < gk); units < ak come from the keeper
-                const int t0 = move_keeper ? 0 : ak;
-                for (int base = t0; base < gk; base += MT_WAVE) {
-                    const int t = base + lane();
-                    int src = 0;
-                    if (t < ak) {
-                        src = (int)bk.x + t;
-                    } else {
-                        // member whose exclusive prefix (relative) is <= t: scan members
-                        for (int j = kk + 1; j <= ge; j++) {
-                            const int rj = bcast(Lm, j) - Lk;
-                            if (t >= rj) src = bcast((int)bm.x, j) + (t - rj);
-                        }
-                    }
-                    uint16_t ch = 0;
-                    if (t < gk) ch = tb[src];
-                    if (t < gk) tb[(move_keeper ? (int)newoff : dst - ak) + t] = ch;
-                }
-            }
+            const v4u bm = d.Bv[k > kk && k <= ge ? s + k : s];   // members: fresh offsets
+            const ScourKeeper r = scour_group(d, bk, ak, bm, a.x, in, g.L, ge, gk, kk);
             if (lane() == 0) {
-                d.A[s + kk].x = gk;
+                d.A[s + kk].x = r.len;
                 v4u nb = bk;
-                nb.x = newoff;
-                nb.w = (lastw & (SEGF_NL_KNOWN | SEGF_NL)) | nonl | (newslack << SEGF_SLACK_SHIFT);
+                nb.x = r.off;
+                nb.w = r.w;
                 d.Bv[s + kk] = nb;
             }
             wsync<T>();

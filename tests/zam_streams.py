@@ -6,13 +6,13 @@ no GPU: configs of the generated streams, the hand-built message logs (compact m
 import random
 
 MT_GRAN = 256   # TextSegment.TextSegmentGranularity: no append to a row longer than this
-MT_WAVE = 64    # rows per gather iteration of scour_merge
+MT_WAVE = 64    # rows per gather iteration of a merge (scour_group)
 
 # ---------------------------------------------------------------- generated streams (harness "gen", ext)
 _ZERO = {"p_insert_props": 0, "p_marker": 0, "p_rewrite": 0, "p_group": 0, "p_noop": 0, "p_empty": 0, "p_oob": 0}
 RANDOM_CONFIGS = {
     # rows far over MT_GRAN and over one wave of text: the serial plan (ScourPlan.big), the
-    # pl.big / p2.big fallbacks of the in-place routes, scour_merge's second gather iteration
+    # pl.big / p2.big fallbacks of the in-place routes, scour_group's second gather iteration
     "ref_zam_long": {"ext": True, "seed": 9143, "ops": 3000, "writers": 6, "lag": 48, "seed_len": 600,
                      "p_insert": 0.45, "p_remove": 0.3, "text_max": 300, "p_newline": 0.002,
                      "p_len_continue": 0.97, "p_insert_props": 0.1, "n_keys": 2, "max_keys_per_op": 1,

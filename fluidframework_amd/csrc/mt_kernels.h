@@ -735,6 +735,7 @@ __global__ void __launch_bounds__(MT_WAVE) k_generate_paged(DevState st, mt_gen_
         gen_pick(g, cfg, t, r, c, msn);
         w.ocs = oslot_of(w, c);
         const int len = pg_views(pd, r, c);
+        if (w.status) break;   // (the view refreshes the window's table entries: capacity)
         if (dbg_len && lane() == 0) {
             int32_t *q = dbg_len + (g.ob + (t - 1)) * 4;
             q[0] = len;

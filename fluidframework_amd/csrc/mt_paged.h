@@ -73,8 +73,9 @@ template <class T> struct PagedDoc {
     int cur;                  // page id staged in the window (-1: none)
     int cur_pos;              // its level-1 position (-1: not known yet)
     int dirty;                // the window differs from the page in HBM (slots, uid map, table)
-    int tdirty;               // an op changed the window since it was loaded: its unsettled-table
-                              // entries are rebuilt at the flush (zamboni's scours / packs change
+    int tdirty;               // an op changed the window since its unsettled-table entries were
+                              // written: they are rebuilt by the next view pass (pg_views_refresh),
+                              // or at the flush if that comes first (zamboni's scours / packs change
                               // settled segments only, whose entries contribute nothing to a view)
     int uid_lo;               // next_uid when the window was loaded: older segments of the
                               // window are already mapped to its page
@@ -879,7 +880,13 @@ TD void pg_split_page(PagedDoc<T> &pd) {
 
 // After a step that modified the window: resolves a pending page split and brings the
 // page's metadata and level-1 count up to date (LDS only; the slots stay in the window).
+TD void pg_win_sync_impl(PagedDoc<T> &pd);
 TD void pg_win_sync(PagedDoc<T> &pd) {
+    PG_T0(44)
+    pg_win_sync_impl(pd);
+    PG_T1(44)
+}
+TD void pg_win_sync_impl(PagedDoc<T> &pd) {
     DocT<T> &w = pd.w;
     DocT<T> &up = pd.up;
     if (pd.cur < 0) return;
@@ -988,9 +995,9 @@ TD void pg_win_switch(PagedDoc<T> &pd, int pg) {
 // ------------------------------------------------------------------ page view lengths
 // A page's length in view (c, r) is its observer length (PageMeta.obs) plus the (view -
 // observer) difference of its unsettled segments: their table entries, or -- when an op has
-// changed the window since it was loaded (tdirty) -- the window's own slots for its page (its
-// entries are rebuilt only at the flush; zamboni's scours change settled segments only, so a
-// window they alone touched keeps exact entries).  Level-1 positions are grouped in chunks of
+// changed the window since its entries were written (tdirty) -- the window's own slots for its
+// page (a view pass that finds it so rebuilds the entries from them, pg_views_refresh; zamboni's
+// scours change settled segments only, so a window they alone touched keeps exact entries).  Level-1 positions are grouped in chunks of
 // 64 whose observer lengths (cob) are kept up to date; a view sums the differences per chunk
 // (cdl, O(table / 64)), and a search picks the chunk, then the page inside it.
 TD int pg_win_delta(PagedDoc<T> &pd, int r, int c) {
@@ -1017,34 +1024,135 @@ TD int pg_views(PagedDoc<T> &pd, int r, int c, bool total = true) {
 TD void pg_views_cached(PagedDoc<T> &pd, int r, int c) {
     if (!(pd.vvalid && pd.vr == r && pd.vc == c)) pg_views(pd, r, c, false);
 }
+// One table entry of the refresh below: kept (compacted to `dst` + its rank among the chunk's
+// kept entries) unless it is settled or names the window's position, and its view difference
+// added to acc[] (pvl by position, or T::kHM: cdl by chunk) exactly as the plain view pass does.
+// A chunk's stores land at or below its own loads and never in a later chunk (pg_table_purge's
+// rule): the caller has loaded every entry it will still read at or above this chunk's stores.
+TD void pg_refresh_chunk(PagedDoc<T> &pd, bool v, int p, const v4i &a, u64 o, const v4i &raw, int wpos, int r, int c,
+                         LDS_AS int *acc, int &dst) {
+    const bool keep = v && p != wpos && unsettled<T>(a, pd.w.min_seq);
+    const int dlt = v && p != wpos ? vlen(pd.w, a, o, r, c) - obs_len(a) : 0;
+    const u64 km = ballot(keep);
+    const int at = dst + __popcll(km & ((1ull << lane()) - 1ull));
+    if (keep) {
+        if constexpr (T::kPacked)
+            tab_raw_put(pd, at, raw);
+        else
+            tab_put(pd, at, p, a, o);
+    }
+    if (dlt) atomicAdd((int *)(acc + (T::kHM ? p >> 6 : p)), dlt);
+    dst += __popcll(km);
+}
+// entry e of a table of n0 (an empty one past its end); packed tables also as stored
+TD void pg_refresh_load(PagedDoc<T> &pd, int e, int n0, int &p, v4i &a, u64 &o, v4i &raw) {
+    p = -1;
+    a = v4i{0, 0, MT_RSEQ_NONE, 0};
+    o = 0;
+    raw = v4i{0, 0, 0, 0};
+    if (e < n0) {
+        tab_get(pd, e, p, a, o);
+        if constexpr (T::kPacked) raw = tab_raw(pd, e);
+    }
+}
+// The view pass over a window an op has changed (tdirty, rows from w.dlo on) rebuilds the
+// window's table entries on the way, as the flush would a few hundred cycles later under the
+// same minSeq, rows and position: one pass over the table (view differences of the other
+// positions' entries, which are compacted over the window's stale and the settled ones) and one
+// over the window's rows (their view differences; the unsettled ones appended under wpos).
+// The flush then finds tdirty == 0 and only writes the page.  Capacity failures are
+// pg_table_add's (w.status; every caller of pg_views checks it).  -DMT_NO_VREFRESH compiles the
+// path out (same-tree A/B): the view then reads the window's rows and the flush rebuilds.
+TD void pg_views_refresh(PagedDoc<T> &pd, int r, int c, int wpos, LDS_AS int *acc) {
+    DocT<T> &w = pd.w;
+    PG_T0(40)
+    int dst = 0;
+    const int n0 = pd.ut_n;
+    for (int base = 0; base < n0; base += MT_WAVE) {
+        int p;
+        v4i a, raw;
+        u64 o;
+        pg_refresh_load(pd, base + lane(), n0, p, a, o, raw);
+        wsync<T>();
+        pg_refresh_chunk(pd, base + lane() < n0, p, a, o, raw, wpos, r, c, acc, dst);
+        wsync<T>();
+    }
+    pd.ut_n = dst;
+    PG_T1(40)
+    PG_T0(41)
+    const int i = lane();
+    const bool v = i < w.n;
+    v4i a;
+    u64 o;
+    load_ao(w, i, v, a, o);
+    const bool add = v && unsettled<T>(a, w.min_seq);
+    const int dlt = wave_sum(v ? vlen(w, a, o, r, c) - obs_len(a) : 0);
+    const u64 m = ballot(add);
+    if (pd.ut_n + __popcll(m) > pd.UT) {
+        pg_fail_cap(w, 8);
+        return;
+    }
+    const int mi = tab_midx(pd, add && o != 0);
+    if (mi < 0) {
+        pg_fail_cap(w, 8);
+        return;
+    }
+    const int at = pd.ut_n + __popcll(m & ((1ull << lane()) - 1ull));
+    if (add) tab_put(pd, at, wpos, a, o, mi);
+    pd.ut_n += __popcll(m);
+    if (lane() == 0) acc[T::kHM ? wpos >> 6 : wpos] += dlt;
+    pd.tdirty = 0;
+    pd.wgrow = pd.opbound;   // exact again, up to the rest of the current message
+    PG_T1(41)
+}
 TD int pg_views_impl(PagedDoc<T> &pd, int r, int c, bool total) {
     const int np = nbr(pd.up, 1);
-    const bool win = pd.cur >= 0 && pd.tdirty;
-    const int wpos = win ? pg_cur_pos(pd) : -1;
+    bool win = pd.cur >= 0 && pd.tdirty;
+    int wpos = win ? pg_cur_pos(pd) : -1;
+#ifndef MT_NO_VREFRESH
+    bool refresh = win;
+#ifndef MT_NO_DIRTY
+    if (win && pd.w.dlo >= pd.w.n) {   // no row changed: the window's entries are exact
+        pd.tdirty = 0;
+        win = refresh = false;
+        wpos = -1;
+    }
+#endif
+#else
+    const bool refresh = false;
+#endif
     if constexpr (!T::kHM) {   // pvl[position] = observer length + differences
+        PG_T0(43)
         for (int base = 0; base < np; base += MT_WAVE) {
             const int q = base + lane();
             if (q < np) pd.pvl[q] = pm_obs(pd, pd.up.dir[q]);
         }
         wsync<T>();
-        PG_T0(36)
-        for (int base = 0; base < pd.ut_n; base += MT_WAVE) {
-            const int e = base + lane();
-            if (e < pd.ut_n) {
-                int pos;
-                v4i a;
-                u64 o;
-                tab_get(pd, e, pos, a, o);
-                const int dlt = vlen(pd.w, a, o, r, c) - obs_len(a);
-                if (dlt && pos != wpos) atomicAdd((int *)(pd.pvl + pos), dlt);
+        PG_T1(43)
+        if (refresh) {
+            pg_views_refresh(pd, r, c, wpos, pd.pvl);
+            wsync<T>();
+            if (pd.w.status) return 0;
+        } else {
+            PG_T0(36)
+            for (int base = 0; base < pd.ut_n; base += MT_WAVE) {
+                const int e = base + lane();
+                if (e < pd.ut_n) {
+                    int pos;
+                    v4i a;
+                    u64 o;
+                    tab_get(pd, e, pos, a, o);
+                    const int dlt = vlen(pd.w, a, o, r, c) - obs_len(a);
+                    if (dlt && pos != wpos) atomicAdd((int *)(pd.pvl + pos), dlt);
+                }
             }
+            PG_T1(36)
+            if (win) {
+                const int dlt = pg_win_delta(pd, r, c);
+                if (lane() == 0) pd.pvl[wpos] += dlt;
+            }
+            wsync<T>();
         }
-        PG_T1(36)
-        if (win) {
-            const int dlt = pg_win_delta(pd, r, c);
-            if (lane() == 0) pd.pvl[wpos] += dlt;
-        }
-        wsync<T>();
 #ifndef MT_VIEWS_TOTAL
         if (!total) return 0;
 #endif
@@ -1057,24 +1165,30 @@ TD int pg_views_impl(PagedDoc<T> &pd, int r, int c, bool total) {
         for (int base = 0; base < nch; base += MT_WAVE)
             if (base + lane() < nch) pd.cdl[base + lane()] = 0;
         wsync<T>();
-        PG_T0(36)
-        for (int base = 0; base < pd.ut_n; base += MT_WAVE) {
-            const int e = base + lane();
-            if (e < pd.ut_n) {
-                int pos;
-                v4i a;
-                u64 o;
-                tab_get(pd, e, pos, a, o);
-                const int dlt = vlen(pd.w, a, o, r, c) - obs_len(a);
-                if (dlt && pos != wpos) atomicAdd((int *)(pd.cdl + (pos >> 6)), dlt);
+        if (refresh) {
+            pg_views_refresh(pd, r, c, wpos, pd.cdl);
+            wsync<T>();
+            if (pd.w.status) return 0;
+        } else {
+            PG_T0(36)
+            for (int base = 0; base < pd.ut_n; base += MT_WAVE) {
+                const int e = base + lane();
+                if (e < pd.ut_n) {
+                    int pos;
+                    v4i a;
+                    u64 o;
+                    tab_get(pd, e, pos, a, o);
+                    const int dlt = vlen(pd.w, a, o, r, c) - obs_len(a);
+                    if (dlt && pos != wpos) atomicAdd((int *)(pd.cdl + (pos >> 6)), dlt);
+                }
             }
+            PG_T1(36)
+            if (win) {
+                const int dlt = pg_win_delta(pd, r, c);
+                if (lane() == 0) pd.cdl[wpos >> 6] += dlt;
+            }
+            wsync<T>();
         }
-        PG_T1(36)
-        if (win) {
-            const int dlt = pg_win_delta(pd, r, c);
-            if (lane() == 0) pd.cdl[wpos >> 6] += dlt;
-        }
-        wsync<T>();
 #ifndef MT_VIEWS_TOTAL
         if (!total) return 0;
 #endif
@@ -1864,6 +1978,7 @@ TD void pg_op_insert(PagedDoc<T> &pd, const OpIn &in, const GLB_AS uint16_t *tin
         if (w.status) return;
     }
     pg_views_cached(pd, op.ref_seq, op_cli(op));
+    if (w.status) return;   // (the view refreshes the window's table entries: capacity)
     int start;
     int ostart;
     int pos = pg_find(pd, op.pos1, false, start, ostart);
@@ -1906,6 +2021,7 @@ TD void pg_op_insert(PagedDoc<T> &pd, const OpIn &in, const GLB_AS uint16_t *tin
 
 TD void pg_boundary(PagedDoc<T> &pd, int p, int r, int c) {
     pg_views_cached(pd, r, c);
+    if (pd.w.status) return;
     int start;
     int ostart;
     const int pos = pg_find(pd, p, true, start, ostart);
@@ -1934,6 +2050,7 @@ TD void pg_op_range(PagedDoc<T> &pd, const mt_op_rec &op, const GLB_AS uint32_t 
     if (w.status) return;
     Cb cb = cb_begin(w, op.seq, op.kind);
     pg_views_cached(pd, r, c);
+    if (w.status) return;
     pd.vvalid = 0;   // range_mark changes view lengths
     int start;
     int ostart;
@@ -1945,7 +2062,9 @@ TD void pg_op_range(PagedDoc<T> &pd, const mt_op_rec &op, const GLB_AS uint32_t 
             pg_load_pos(pd, pos, ocarry);
             if (w.status) return;
             pd.tdirty = 1;
+            PG_T0(45)
             const bool done = range_mark(w, op, rec, carry, ocarry, cb);
+            PG_T1(45)
             if (w.status) return;
             pg_win_sync(pd);
             if (w.status) return;
@@ -2448,6 +2567,7 @@ TD int pg_ovf_need_counted(PagedDoc<T> &pd, const mt_op_rec &op) {
     const int r = op.ref_seq, c = op_cli(op);
     w.ocs = oslot_of(w, c);   // (as pg_apply_op_impl sets it: the view's own slot)
     pg_views_cached(pd, r, c);
+    if (w.status) return 1 << 30;
     int start, ostart;
     const int np = nbr(pd.up, 1);
     const int p1 = pg_find(pd, op.pos1, true, start, ostart);

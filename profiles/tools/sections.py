@@ -39,7 +39,9 @@ ops = docs * cfg["ops"]
 names += [""] * (64 - len(names))
 for k, n in {26: "scour need_nl", 27: "scour text merge", 28: "scour compaction", 29: "flat zamboni find",
              30: "insert split pass", 31: "(p2 14)", 32: "insert seg shift", 33: "flush purge",
-             34: "flush table add", 35: "flush write page", 36: "pg_views table"}.items():
+             34: "flush table add", 35: "flush write page", 36: "pg_views table",
+             40: "views refresh table", 41: "views refresh window", 43: "pg_views pvl init",
+             44: "pg_win_sync", 45: "range_mark"}.items():
     names[k] = n
 for i, n in enumerate(names):
     if n and out[64 + i]:

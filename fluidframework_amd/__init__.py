@@ -666,6 +666,86 @@ class MergeTreeBatch:
                                                  _native.ptr(cli), _native.ptr(out)), "mt_get_view_lengths")
         return out
 
+    # bulk segment read-outs (mt_locate_segments / mt_locate_uids / mt_get_view_lengths_bulk /
+    # mt_resolve_remote_positions): the three calls above for many cursors in one launch
+    def _cursor_queries(self, docs, key, ref_seq, client, key_dtype):
+        """(n, docs, key, ref_seq, client) as mt_locate_* take them; scalars broadcast; ref_seq /
+        client None: the observer view for every query."""
+        if docs is not None:
+            docs = np.ascontiguousarray(docs, dtype=np.uint32).reshape(-1)
+        n = len(docs) if docs is not None else self.n_docs
+        if key is not None:
+            key = np.ascontiguousarray(np.broadcast_to(np.asarray(key, dtype=key_dtype), (n,)))
+        if client is None:
+            ref_seq = None
+        else:
+            client = np.ascontiguousarray(np.broadcast_to(np.asarray(client, dtype=np.int32), (n,)))
+            ref_seq = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if ref_seq is None else ref_seq,
+                                                                      dtype=np.int32), (n,)))
+        return n, docs, key, ref_seq, client
+
+    def locate_segments(self, docs, pos, ref_seq=None, client=None):
+        """MergeTree.getContainingSegment(pos, refSeq, clientId) for each (doc, pos, refSeq,
+        client): a structured array of mt_seg_hit records (_native.SEG_HIT_DTYPE; row -1: no
+        segment; `local_position`: the segment's position in the observer view)."""
+        n, docs, pos, ref, cli = self._cursor_queries(docs, pos, ref_seq, client, np.int32)
+        out = np.zeros(n, dtype=_native.SEG_HIT_DTYPE)
+        self._check(self.lib.mt_locate_segments(self.h, n, _native.ptr(docs), _native.ptr(pos), _native.ptr(ref),
+                                                _native.ptr(cli), _native.ptr(out)), "mt_locate_segments")
+        return out
+
+    def locate_uids(self, docs, uids, ref_seq=None, client=None):
+        """MergeTree.getPosition(segment, refSeq, clientId) of the segments with ids `uids`, as
+        locate_segments' records (offset 0; row -1 once a segment left the tree)."""
+        n, docs, uids, ref, cli = self._cursor_queries(docs, uids, ref_seq, client, np.uint32)
+        out = np.zeros(n, dtype=_native.SEG_HIT_DTYPE)
+        self._check(self.lib.mt_locate_uids(self.h, n, _native.ptr(docs), _native.ptr(uids), _native.ptr(ref),
+                                            _native.ptr(cli), _native.ptr(out)), "mt_locate_uids")
+        return out
+
+    def locate_segments_device(self, docs, pos=None, ref_seq=None, client=None, uids=None):
+        """locate_segments (or, with uids, locate_uids) with the records left on the handle's
+        device: an int32 torch tensor [n, 12], the words of mt_seg_hit in order (torch is imported
+        before the first handle is created, as for get_texts_device)."""
+        import torch
+        by_uid = uids is not None
+        n, docs, key, ref, cli = self._cursor_queries(docs, uids if by_uid else pos, ref_seq, client,
+                                                      np.uint32 if by_uid else np.int32)
+        out = torch.empty((n, _native.SEG_HIT_DTYPE.itemsize // 4), dtype=torch.int32,
+                          device=torch.device("cuda", self.device))
+        fn, name = ((self.lib.mt_locate_uids_device, "mt_locate_uids_device") if by_uid
+                    else (self.lib.mt_locate_segments_device, "mt_locate_segments_device"))
+        self._check(fn(self.h, n, _native.ptr(docs), _native.ptr(key), _native.ptr(ref), _native.ptr(cli),
+                       ctypes.c_void_p(out.data_ptr())), name)
+        return out
+
+    def get_view_lengths_bulk(self, docs, ref_seq=None, client=None):
+        """get_view_lengths summed on the device, one launch for all queries."""
+        n, docs, _, ref, cli = self._cursor_queries(docs, None, ref_seq, client, np.int32)
+        out = np.zeros(n, dtype=np.int32)
+        self._check(self.lib.mt_get_view_lengths_bulk(self.h, n, _native.ptr(docs), _native.ptr(ref), _native.ptr(cli),
+                                                      _native.ptr(out)), "mt_get_view_lengths_bulk")
+        return out
+
+    def resolve_remote_positions(self, docs, pos, ref_seq, client):
+        """MergeTree.resolveRemoteClientPosition(pos, refSeq, clientId) (MT/mergeTree.ts:2140-2160)
+        for each query: the position in the observer view, -1 where the reference returns
+        undefined."""
+        n, docs, pos, ref, cli = self._cursor_queries(docs, pos, ref_seq, client, np.int32)
+        out = np.zeros(n, dtype=np.int32)
+        self._check(self.lib.mt_resolve_remote_positions(self.h, n, _native.ptr(docs), _native.ptr(pos),
+                                                         _native.ptr(ref), _native.ptr(cli), _native.ptr(out)),
+                    "mt_resolve_remote_positions")
+        return out
+
+    def last_locate(self):
+        """(queries, of them answered by the host path, kernel ms) of the last bulk segment
+        read-out."""
+        out = np.zeros(2, dtype=np.int64)
+        ms = ctypes.c_float()
+        self._check(self.lib.mt_last_locate(self.h, _native.ptr(out), ctypes.byref(ms)), "mt_last_locate")
+        return int(out[0]), int(out[1]), float(ms.value)
+
     def get_prop_runs(self, doc):
         nr, nw = ctypes.c_uint32(), ctypes.c_uint32()
         self._check(self.lib.mt_get_prop_runs(self.h, doc, None, 0, ctypes.byref(nr), None, 0,

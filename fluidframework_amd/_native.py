@@ -44,6 +44,14 @@ REGEN_DTYPE = np.dtype([("kind", "<i4"), ("pos1", "<i4"), ("pos2", "<i4"), ("loc
                         ("text_off", "<u4"), ("text_len", "<u4"), ("props_off", "<u4"), ("flags", "<u4")])
 
 
+# mt_seg_hit (include/mt_replay.h): one record of the bulk segment read-outs
+SEG_HIT_DTYPE = np.dtype([("row", "<i4"), ("uid", "<u4"), ("position", "<i4"), ("offset", "<i4"),
+                          ("local_position", "<i4"), ("length", "<i4"), ("seq", "<i4"), ("client", "<i4"),
+                          ("removed_seq", "<i4"), ("removed_client", "<i4"), ("marker_ref_type", "<i4"),
+                          ("flags", "<u4")])
+MT_HIT_HOST = 1
+
+
 class MtGenCfg(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint32), ("ops", ctypes.c_int32), ("writers", ctypes.c_int32),
                 ("lag", ctypes.c_int32), ("seed_len", ctypes.c_int32), ("text_max", ctypes.c_int32),
@@ -119,6 +127,13 @@ SIGNATURES = [
     ("mt_get_containing_segment", _I, [_P, _U32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _U32]),
     ("mt_get_segment_by_uid", _I, [_P, _U32, _U32, ctypes.c_int32, ctypes.c_int32, _P, _P, _U32]),
     ("mt_get_view_lengths", _I, [_P, _U32, _P, _P, _P, _P]),
+    ("mt_locate_segments", _I, [_P, _U32, _P, _P, _P, _P, _P]),
+    ("mt_locate_uids", _I, [_P, _U32, _P, _P, _P, _P, _P]),
+    ("mt_locate_segments_device", _I, [_P, _U32, _P, _P, _P, _P, _P]),
+    ("mt_locate_uids_device", _I, [_P, _U32, _P, _P, _P, _P, _P]),
+    ("mt_get_view_lengths_bulk", _I, [_P, _U32, _P, _P, _P, _P]),
+    ("mt_resolve_remote_positions", _I, [_P, _U32, _P, _P, _P, _P, _P]),
+    ("mt_last_locate", _I, [_P, _P, _P]),
 ]
 
 _lib = None

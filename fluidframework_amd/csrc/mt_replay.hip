@@ -213,6 +213,7 @@ __device__ static u64 fold_run(const uint32_t *pr, u64 h, uint32_t ph, int len) 
 struct SegRanges {
     const v4i *A;
     const v4u *B;
+    const u64 *O;   // overlap masks (the view read-outs)
     int n;
     bool paged;
     const uint16_t *dir;
@@ -239,6 +240,7 @@ __device__ static SegRanges seg_ranges(const DevState &st, int doc, const DocHdr
         const PagedBase b = doc_paged(st, doc);
         R.A = b.A;
         R.B = b.B;
+        R.O = b.O;
         R.dir = b.dir;
         R.meta = b.meta;
         R.nr = h.pad[HDR_NPAGES];
@@ -246,6 +248,7 @@ __device__ static SegRanges seg_ranges(const DevState &st, int doc, const DocHdr
     } else {
         R.A = st.segA + doc * (size_t)st.S;
         R.B = st.segB + doc * (size_t)st.S;
+        R.O = st.segO + doc * (size_t)st.S;
         R.n = h.n_seg;
         R.nr = 1;
         R.dir = nullptr;
@@ -788,6 +791,190 @@ __global__ void __launch_bounds__(MT_WAVE) k_props_gather(DevState st, int nq, c
     if (open_row >= 0 && open_row < room_r && lane() == 0) rows[3 * open_row + 1] = (uint32_t)(Q.s + done - open_pos);
 }
 
+// ---------------------------------------------------------------- bulk segment read-outs
+// MergeTree.getContainingSegment / getPosition / getLength (MT/mergeTree.ts:1610-1667) for many
+// (doc, pos | uid, refSeq, client) queries: one wave per query over the document's rows in
+// chunks of 64, as k_text_count walks.  In a view (c, r) a row is inserted (ins) and removed
+// (gone) by view_len's two tests, with the overflow set read when the mask carries MT_OVF_BIT
+// (ovf_member, host_view_vis).  One walk sums
+//     N = sum len * (ins - gone)   -- the root's partial length, getLength in the view
+//     L = sum view_len             -- the leaves' lengths
+// N = L - (the lengths of the rows with gone and not ins), so N == L exactly when no row of
+// positive length is removed but not inserted in the view; every interior partial length is
+// then the sum of its leaves' view lengths, all of them >= 0, and searchBlock's descent (the
+// first child whose length exceeds pos, at every level) ends at the first row whose inclusive
+// view_len prefix exceeds pos -- or at none when pos >= L -- and getPosition is the exclusive
+// prefix.  Otherwise the query is marked for the host path.
+// Observer view (c == 0): N == L always; the walk stops at the answer's chunk and, on a paged
+// document, finds the page by the directory's PageMeta.obs prefix sums (by position) or by the
+// uid map (a hint: the page must be in the directory and hold the uid, else the rows are
+// walked) and reads that page's rows only.
+#define MT_LOC_HOST 1      // aux mark: a view with N != L, answered on the host
+#define MT_LOC_INVALID 2   // aux mark: a remote refSeq outside [minSeq, currentSeq]
+static_assert(sizeof(mt_seg_hit) == 48, "mt_seg_hit size");
+struct LocWalk {           // wave-uniform
+    int vpos, opos, rows;  // view / observer length and rows before the current range
+    int nacc;              // (per lane) its rows' terms of N
+    bool found;
+    mt_seg_hit hit;
+};
+__device__ static bool loc_ovf_member(const uint16_t *ovf, int OA, u64 o, int c) {
+    const uint32_t off = (uint32_t)o;
+    if (!ovf || off >= (uint32_t)OA) return false;
+    const uint32_t n = ovf[off];
+    bool in = false;
+    for (uint32_t k = 1; k <= n && off + k < (uint32_t)OA; k++) in = in | (ovf[off + k] == (uint16_t)c);
+    return in;
+}
+// rows [base, base + 64) of a range of n rows (kMode 0: locate position key, 1: locate uid key,
+// 2: lengths only)
+template <int kMode>
+__device__ __forceinline__ void loc_chunk(LocWalk &W, const v4i *A, const u64 *O, const v4u *Bv, int base, int n, int key,
+                                          bool local, int r, int c, int cs, const uint16_t *ovf, int OA) {
+    const int i = base + lane();
+    const bool v = i < n;
+    const int ic = v ? i : 0;
+    v4i a = A[ic];
+    u64 o = O[ic];   // (unconditional: DESIGN section 10)
+    v4u b = v4u{0u, 0u, 0u, 0u};
+    if (kMode != 2) b = Bv[ic];
+    if (!v) {
+        a = v4i{0, 0, MT_RSEQ_NONE, 0};
+        o = 0ull;
+    }
+    const int ol = obs_len(a);
+    int vl = ol, pl = ol;
+    if (!local) {
+        bool ovl = ovl_has(o, cs);
+        if (o & MT_OVF_BIT) ovl = loc_ovf_member(ovf, OA, o, c);
+        const bool ins = (seg_cli(a) == c) | ((a.y != -1) & (a.y <= r));
+        const bool gone = (a.z != MT_RSEQ_NONE) & ((seg_rcli(a) == c) | ovl | ((a.z != -1) & (a.z <= r)));
+        vl = (ins & !gone) ? a.x : 0;
+        pl = a.x * ((int)ins - (int)gone);
+    }
+    W.nacc += pl;
+    const int vin = wave_scan_incl(vl);
+    const int oin = local ? vin : wave_scan_incl(ol);
+    if (kMode != 2 && !W.found) {
+        const u64 m = kMode == 0 ? ballot(v & (W.vpos + vin > key)) : ballot(v & ((b.z & ~MT_MARKER_BIT) == (uint32_t)key));
+        if (m) {
+            const int l = first_lane(m);
+            const int x = bcast(a.x, l), y = bcast(a.y, l), z = bcast(a.z, l), w = bcast(a.w, l);
+            const uint32_t bx = (uint32_t)bcast((int)b.x, l), bz = (uint32_t)bcast((int)b.z, l);
+            W.found = true;
+            W.hit.row = W.rows + base + l;
+            W.hit.uid = bz & ~MT_MARKER_BIT;
+            W.hit.position = W.vpos + bcast(vin - vl, l);
+            W.hit.offset = kMode == 0 ? key - W.hit.position : 0;
+            W.hit.local_position = W.opos + bcast(oin - ol, l);
+            W.hit.length = x;
+            W.hit.seq = y >= MT_LOCAL_BASE ? -1 : y;
+            W.hit.client = (int)(short)(w & 0xFFFF);
+            W.hit.removed_seq = z >= MT_LOCAL_BASE ? -1 : z;
+            W.hit.removed_client = z == MT_RSEQ_NONE ? MT_RSEQ_NONE : (int)(short)((uint32_t)w >> 16);
+            W.hit.marker_ref_type = (bz & MT_MARKER_BIT) ? (int32_t)bx : -1;
+        }
+    }
+    W.vpos += bcast(vin, 63);
+    W.opos += bcast(oin, 63);
+}
+template <int kMode>
+__global__ void __launch_bounds__(MT_WAVE) k_locate(DevState st, int nq, const uint32_t *docs, const int32_t *key,
+                                                    const int32_t *ref_seq, const int32_t *client, int skip,
+                                                    mt_seg_hit *out, v4i *aux) {
+    const int q = blockIdx.x;
+    if (q >= nq) return;
+    const int doc = docs ? (int)docs[q] : q;
+    const int c = client ? client[q] : 0;
+    const int r = ref_seq ? ref_seq[q] : 0;
+    const int k = kMode == 2 ? 0 : key[q];
+    const bool local = c == 0;
+    LocWalk W;
+    memset(&W.hit, 0, sizeof(W.hit));
+    W.hit.row = -1;
+    W.vpos = W.opos = W.rows = W.nacc = 0;
+    W.found = false;
+    int mark = 0, N = 0;
+    if (doc < 0 || doc >= st.n_docs) {   // (the host refuses these)
+        mark = MT_LOC_INVALID;
+    } else {
+        const DocHdr h = st.hdr[doc];
+        if (!local && (r < h.min_seq || r > h.cur_seq)) {
+            mark = MT_LOC_INVALID;
+        } else {
+            const u64 sm = ballot(st.oslot[((size_t)doc * MT_OSLOTS + lane()) * 2] == c);
+            const int cs = !local && sm ? first_lane(sm) + 1 : 0;
+            const SegRanges R = seg_ranges(st, doc, h);
+            const uint16_t *ovf = nullptr, *umap = nullptr;
+            int OA = 0, UM = 0, PP = 0;
+            if (R.paged) {
+                const PagedBase pb = doc_paged(st, doc);
+                ovf = pb.ovf;
+                OA = pb.OA;
+                umap = pb.umap;
+                UM = pb.UM;
+                PP = pb.PP;
+            }
+            bool walk = true;
+            if (local && R.paged && skip) {
+                // the page by the directory (64 positions at a time); by uid: the page the map names
+                int target = -1;
+                if (kMode == 1 && (uint32_t)k < (uint32_t)UM) target = umap[(uint32_t)k];
+                if (target >= PP) target = -1;
+                walk = kMode == 1 && target < 0;
+                bool at = false;
+                for (int base = 0; !walk && !at && base < R.nr; base += MT_WAVE) {
+                    const int j = base + lane();
+                    const bool v = j < R.nr;
+                    const int pg = R.dir[v ? j : 0];
+                    const PageMeta pm = R.meta[pg];
+                    const int ob = v ? pm.obs : 0, ns = v ? (int)pm.nseg : 0;
+                    const int oin = wave_scan_incl(ob), nin = wave_scan_incl(ns);
+                    const u64 m = kMode == 0 ? ballot(v & (W.opos + oin > k)) : (kMode == 1 ? ballot(v & (pg == target)) : 0ull);
+                    if (m) {
+                        const int l = first_lane(m);
+                        const size_t p0 = (size_t)bcast(pg, l) * MT_PG_SLOTS;
+                        W.opos += bcast(oin - ob, l);
+                        W.rows += bcast(nin - ns, l);
+                        W.vpos = W.opos;
+                        loc_chunk<kMode>(W, R.A + p0, R.O + p0, R.B + p0, 0, min(bcast(ns, l), MT_PG_SLOTS), k, true, r, c, 0,
+                                         ovf, OA);
+                        at = true;
+                    } else {
+                        W.opos += bcast(oin, 63);
+                        W.rows += bcast(nin, 63);
+                        W.vpos = W.opos;
+                    }
+                }
+                // no page holds it: past the end by position (the directory's total is the length);
+                // by uid the map was stale or the page not the segment's: walk the rows
+                if (kMode == 1 && !W.found) walk = true;
+                if (kMode == 0 && at && !W.found) walk = true;   // (obs and the page's rows disagree: never seen)
+                if (walk) W.vpos = W.opos = W.rows = W.nacc = 0;
+            }
+            if (walk) {
+                for (int rr = 0; rr < R.count() && !(local && W.found); rr++) {
+                    const v4i *A;
+                    const v4u *Bv;
+                    int n;
+                    R.get(rr, A, Bv, n);
+                    const u64 *O = R.O + (A - R.A);
+                    for (int base = 0; base < n && !(local && W.found); base += MT_WAVE)
+                        loc_chunk<kMode>(W, A, O, Bv, base, n, k, local, r, c, cs, ovf, OA);
+                    W.rows += n;
+                }
+            }
+            // (observer view: N == L; the sum is whole only when the walk did not stop at a hit)
+            N = local ? W.vpos : wave_sum(W.nacc);
+            if (kMode != 2 && N != W.vpos) mark = MT_LOC_HOST;
+        }
+    }
+    if (lane() == 0) {
+        if (kMode != 2) out[q] = W.hit;
+        aux[q] = v4i{mark, N, W.opos, 0};
+    }
+}
+
 // ============================================================================ host side
 // ---------------------------------------------------------------- live-client reconnect
 // regeneratePendingOp for the oldest pending segment group of one document (one wave):
@@ -939,6 +1126,9 @@ struct mt_handle {
     int txt_timed = 0;         // 1: the counting pass was bracketed, 2: the gather as well
     hipEvent_t ev_prp[4] = {nullptr, nullptr, nullptr, nullptr};   // mt_get_prop_runs_bulk: the same two brackets
     int prp_timed = 0;
+    hipEvent_t ev_loc[2] = {nullptr, nullptr};   // the bulk segment read-outs' kernel
+    bool loc_timed = false;
+    int64_t loc_n = 0, loc_host = 0;   // queries of the last one, of them answered by the host path
     // documents per workgroup of the LDS-tier replay (env MT_WPG=2 for two): measured on C2
     // the CU saturates at 16 resident documents (16 -> 18 per CU: 61.8 -> 64.6 ms)
     int wpg = 1;
@@ -1312,6 +1502,8 @@ void mt_destroy(mt_handle *h) {
     for (hipEvent_t e : h->ev_txt)
         if (e) hipEventDestroy(e);
     for (hipEvent_t e : h->ev_prp)
+        if (e) hipEventDestroy(e);
+    for (hipEvent_t e : h->ev_loc)
         if (e) hipEventDestroy(e);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -3422,22 +3614,11 @@ static int host_seg_info(mt_handle *h, uint32_t doc, const HostDoc &hd, int i, m
     return 0;
 }
 
-int mt_get_containing_segment(mt_handle *h, uint32_t doc, int32_t pos, int32_t ref_seq, int32_t client,
-                              mt_seg_info *out, uint16_t *text, uint32_t text_cap) {
-    if (!out) return MT_E_INVALID;
-    HostDoc hd;
-    int rc = fetch_doc(h, doc, hd, text != nullptr, false);
-    if (rc) return rc;
-    HostView v;
-    if ((rc = host_view_setup(h, doc, hd, ref_seq, client, v))) return rc;
-    memset(out, 0, sizeof(*out));
-    out->row = -1;
-    if (hd.hdr.n_seg == 0 || hd.lv.empty()) return 0;
-    // searchBlock (:1830-1862): at every level the first child with pos < nodeLength(child),
-    // interior children by their partial lengths; no backtracking (a block whose leaves do not
-    // hold pos yields no segment)
-    HostTree t;
-    host_tree(hd, v, t);
+// searchBlock (:1830-1862) for pos in view v: at every level the first child with
+// pos < nodeLength(child), interior children by their partial lengths; no backtracking (a block
+// whose leaves do not hold pos yields no segment).  The row (-1: none) and the offset into it.
+static int host_search(const HostDoc &hd, const HostView &v, const HostTree &t, int pos, int &offset) {
+    if (hd.hdr.n_seg == 0 || hd.lv.empty()) return -1;
     const int D = (int)hd.lv.size();
     int b = 0;
     for (int l = D - 1; l >= 1; l--) {
@@ -3449,19 +3630,39 @@ int mt_get_containing_segment(mt_handle *h, uint32_t doc, int32_t pos, int32_t r
             }
             pos -= t.P[l - 1][k];
         }
-        if (hit < 0) return 0;
+        if (hit < 0) return -1;
         b = hit;
     }
     for (int i = t.first[0][b]; i < t.first[0][b] + hd.lv[0][b] && i < hd.hdr.n_seg; i++) {
         const int l = host_view_len(hd, v, i);
         if (pos < l) {
-            host_seg_info(h, doc, hd, i, out, text, text_cap);
-            out->position = host_position(hd, v, t, i);
-            out->offset = pos;
-            return 0;
+            offset = pos;
+            return i;
         }
         pos -= l;
     }
+    return -1;
+}
+
+int mt_get_containing_segment(mt_handle *h, uint32_t doc, int32_t pos, int32_t ref_seq, int32_t client,
+                              mt_seg_info *out, uint16_t *text, uint32_t text_cap) {
+    if (!out) return MT_E_INVALID;
+    HostDoc hd;
+    int rc = fetch_doc(h, doc, hd, text != nullptr, false);
+    if (rc) return rc;
+    HostView v;
+    if ((rc = host_view_setup(h, doc, hd, ref_seq, client, v))) return rc;
+    memset(out, 0, sizeof(*out));
+    out->row = -1;
+    if (hd.hdr.n_seg == 0 || hd.lv.empty()) return 0;
+    HostTree t;
+    host_tree(hd, v, t);
+    int offset = 0;
+    const int i = host_search(hd, v, t, pos, offset);
+    if (i < 0) return 0;
+    host_seg_info(h, doc, hd, i, out, text, text_cap);
+    out->position = host_position(hd, v, t, i);
+    out->offset = offset;
     return 0;
 }
 
@@ -3504,6 +3705,202 @@ int mt_get_view_lengths(mt_handle *h, uint32_t n, const uint32_t *docs, const in
         int len = 0;
         for (int i = 0; i < hd.hdr.n_seg; i++) len += host_seg_partial(hd, v, i);
         out[q] = len;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- bulk segment read-outs
+// mt_locate_segments / mt_locate_uids / mt_get_view_lengths_bulk / mt_resolve_remote_positions:
+// one k_locate launch; the per-query marks come back with the view lengths (aux), and the
+// queries the kernel marked MT_LOC_HOST are answered here from the single-query calls' code,
+// grouped so that each document is fetched once and each view's tree built once.
+namespace {
+enum { LOC_POS = 0, LOC_UID = 1, LOC_LEN = 2 };
+}
+static int locate(mt_handle *h, const char *name, int mode, uint32_t n, const uint32_t *docs, const int32_t *key,
+                  const int32_t *ref_seq, const int32_t *client, mt_seg_hit *out, void *out_dev, bool device,
+                  std::vector<int4> *aux_out) {
+    if (!h || n > 0x7FFFFFFFu) return MT_E_INVALID;
+    if (n && mode != LOC_LEN && (!key || (device ? !out_dev : !out))) return MT_E_INVALID;
+    if ((ref_seq == nullptr) != (client == nullptr)) return MT_E_INVALID;
+    if (!docs && n > h->n_docs) return MT_E_INVALID;
+    for (uint32_t q = 0; q < n; q++) {
+        if (docs && docs[q] >= h->n_docs) {
+            h->err = std::string(name) + ": query " + std::to_string(q) + ": no document " + std::to_string(docs[q]);
+            return MT_E_INVALID;
+        }
+        if (mode == LOC_POS && key[q] < 0) {
+            h->err = std::string(name) + ": query " + std::to_string(q) + ": negative position";
+            return MT_E_INVALID;
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    SETTLE(h);
+    h->loc_timed = false;
+    h->loc_n = n;
+    h->loc_host = 0;
+    if (aux_out) aux_out->clear();
+    if (n == 0) return 0;
+    for (hipEvent_t &e : h->ev_loc)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    // one allocation: aux[n] (16 bytes each), the records (host results), [docs | key | ref_seq | client]
+    DevBuf buf;
+    const size_t aux_b = (size_t)n * sizeof(int4), hit_b = mode != LOC_LEN && !device ? (size_t)n * sizeof(mt_seg_hit) : 0;
+    HIPCHK(h, hipMalloc(&buf.p, aux_b + hit_b + (size_t)n * 16));
+    v4i *d_aux = (v4i *)buf.p;
+    mt_seg_hit *d_hit = device ? (mt_seg_hit *)out_dev : (mt_seg_hit *)((char *)buf.p + aux_b);
+    uint32_t *d_docs = (uint32_t *)((char *)buf.p + aux_b + hit_b);
+    int32_t *d_key = (int32_t *)d_docs + n, *d_ref = d_key + n, *d_cli = d_ref + n;
+    if (docs) HIPCHK(h, hipMemcpy(d_docs, docs, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (key) HIPCHK(h, hipMemcpy(d_key, key, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (ref_seq) HIPCHK(h, hipMemcpy(d_ref, ref_seq, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (client) HIPCHK(h, hipMemcpy(d_cli, client, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (!docs) d_docs = nullptr;
+    if (!ref_seq) d_ref = d_cli = nullptr;
+    // MT_LOCATE_ROW_WALK=1: observer-view queries walk every row (the A/B of tools/cursor_probe.py)
+    const char *rw = getenv("MT_LOCATE_ROW_WALK");
+    const int skip = !(rw && rw[0] == '1');
+    HIPCHK(h, hipEventRecord(h->ev_loc[0], h->stream));
+    if (mode == LOC_POS)
+        hipLaunchKernelGGL(k_locate<0>, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_key, d_ref, d_cli,
+                           skip, d_hit, d_aux);
+    else if (mode == LOC_UID)
+        hipLaunchKernelGGL(k_locate<1>, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_key, d_ref, d_cli,
+                           skip, d_hit, d_aux);
+    else
+        hipLaunchKernelGGL(k_locate<2>, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_key, d_ref, d_cli,
+                           skip, (mt_seg_hit *)nullptr, d_aux);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev_loc[1], h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->loc_timed = true;
+    std::vector<int4> aux(n);
+    HIPCHK(h, hipMemcpy(aux.data(), d_aux, aux_b, hipMemcpyDeviceToHost));
+    for (uint32_t q = 0; q < n; q++)
+        if (aux[q].x == MT_LOC_INVALID) {
+            h->err = std::string(name) + ": query " + std::to_string(q) + ": remote view of document " +
+                     std::to_string(docs ? docs[q] : q) + " with refSeq " + std::to_string(ref_seq[q]) +
+                     " outside the collab window [minSeq, currentSeq]";
+            return MT_E_INVALID;
+        }
+    if (hit_b) HIPCHK(h, hipMemcpy(out, d_hit, hit_b, hipMemcpyDeviceToHost));
+    // the host path
+    std::vector<uint32_t> todo;
+    for (uint32_t q = 0; q < n; q++)
+        if (aux[q].x == MT_LOC_HOST) todo.push_back(q);
+    auto doc_of = [&](uint32_t q) { return docs ? docs[q] : q; };
+    std::stable_sort(todo.begin(), todo.end(), [&](uint32_t a, uint32_t b) {
+        if (doc_of(a) != doc_of(b)) return doc_of(a) < doc_of(b);
+        if (client[a] != client[b]) return client[a] < client[b];
+        return ref_seq[a] < ref_seq[b];
+    });
+    HostDoc hd;
+    HostView v{0, 0, 0, false};
+    const HostView obs{0, 0, 0, true};
+    HostTree t, tl;
+    int64_t have = -1, have_c = 0, have_r = 0;
+    for (uint32_t q : todo) {
+        const uint32_t d = doc_of(q);
+        int rc;
+        bool fresh = false;
+        if ((int64_t)d != have) {
+            if ((rc = fetch_doc(h, d, hd, false, false))) return rc;
+            host_tree(hd, obs, tl);
+            have = d;
+            fresh = true;
+        }
+        if (fresh || client[q] != have_c || ref_seq[q] != have_r) {
+            if ((rc = host_view_setup(h, d, hd, ref_seq[q], client[q], v))) return rc;
+            host_tree(hd, v, t);
+            have_c = client[q];
+            have_r = ref_seq[q];
+        }
+        mt_seg_hit rec;
+        memset(&rec, 0, sizeof(rec));
+        rec.row = -1;
+        rec.flags = MT_HIT_HOST;
+        int row = -1, off = 0;
+        if (mode == LOC_POS) {
+            row = host_search(hd, v, t, key[q], off);
+        } else {
+            for (int i = 0; i < hd.hdr.n_seg && row < 0; i++)
+                if ((hd.B[i].z & ~MT_MARKER_BIT) == (uint32_t)key[q]) row = i;
+        }
+        if (row >= 0) {
+            mt_seg_info si;
+            memset(&si, 0, sizeof(si));
+            if ((rc = host_seg_info(h, d, hd, row, &si, nullptr, 0))) return rc;
+            rec.row = si.row;
+            rec.uid = si.uid;
+            rec.position = host_position(hd, v, t, row);
+            rec.offset = off;
+            rec.local_position = host_position(hd, obs, tl, row);
+            rec.length = si.length;
+            rec.seq = si.seq;
+            rec.client = si.client;
+            rec.removed_seq = si.removed_seq;
+            rec.removed_client = si.removed_client;
+            rec.marker_ref_type = si.marker_ref_type;
+        }
+        if (device)
+            HIPCHK(h, hipMemcpy((mt_seg_hit *)out_dev + q, &rec, sizeof(rec), hipMemcpyHostToDevice));
+        else
+            out[q] = rec;
+    }
+    h->loc_host = (int64_t)todo.size();
+    if (aux_out) *aux_out = std::move(aux);
+    return 0;
+}
+
+int mt_locate_segments(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *pos, const int32_t *ref_seq,
+                       const int32_t *client, mt_seg_hit *out) {
+    return locate(h, "mt_locate_segments", LOC_POS, n, docs, pos, ref_seq, client, out, nullptr, false, nullptr);
+}
+int mt_locate_uids(mt_handle *h, uint32_t n, const uint32_t *docs, const uint32_t *uids, const int32_t *ref_seq,
+                   const int32_t *client, mt_seg_hit *out) {
+    return locate(h, "mt_locate_uids", LOC_UID, n, docs, (const int32_t *)uids, ref_seq, client, out, nullptr, false,
+                  nullptr);
+}
+int mt_locate_segments_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *pos,
+                              const int32_t *ref_seq, const int32_t *client, void *out_dev) {
+    return locate(h, "mt_locate_segments_device", LOC_POS, n, docs, pos, ref_seq, client, nullptr, out_dev, true,
+                  nullptr);
+}
+int mt_locate_uids_device(mt_handle *h, uint32_t n, const uint32_t *docs, const uint32_t *uids, const int32_t *ref_seq,
+                          const int32_t *client, void *out_dev) {
+    return locate(h, "mt_locate_uids_device", LOC_UID, n, docs, (const int32_t *)uids, ref_seq, client, nullptr, out_dev,
+                  true, nullptr);
+}
+int mt_get_view_lengths_bulk(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *ref_seq,
+                             const int32_t *client, int32_t *out) {
+    if (n && !out) return MT_E_INVALID;
+    std::vector<int4> aux;
+    const int rc = locate(h, "mt_get_view_lengths_bulk", LOC_LEN, n, docs, nullptr, ref_seq, client, nullptr, nullptr,
+                          false, &aux);
+    if (rc) return rc;
+    for (uint32_t q = 0; q < n; q++) out[q] = aux[q].y;
+    return 0;
+}
+int mt_resolve_remote_positions(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *pos,
+                                const int32_t *ref_seq, const int32_t *client, int32_t *out) {
+    if (n && !out) return MT_E_INVALID;
+    std::vector<mt_seg_hit> hits(std::max<uint32_t>(n, 1));
+    std::vector<int4> aux;
+    const int rc = locate(h, "mt_resolve_remote_positions", LOC_POS, n, docs, pos, ref_seq, client, hits.data(), nullptr,
+                          false, &aux);
+    if (rc) return rc;
+    // (aux: {mark, the view's length, the observer length when the walk found no segment})
+    for (uint32_t q = 0; q < n; q++)
+        out[q] = hits[q].row >= 0 ? hits[q].local_position + hits[q].offset : (pos[q] == aux[q].y ? aux[q].z : -1);
+    return 0;
+}
+int mt_last_locate(mt_handle *h, int64_t *out, float *ms) {
+    if (!h || !out) return MT_E_INVALID;
+    out[0] = h->loc_n;
+    out[1] = h->loc_host;
+    if (ms) {
+        *ms = 0.f;
+        if (h->loc_timed) HIPCHK(h, hipEventElapsedTime(ms, h->ev_loc[0], h->ev_loc[1]));
     }
     return 0;
 }

@@ -647,6 +647,63 @@ napi_value GetPropRunsBulk(napi_env env, napi_callback_info info) {
     return obj;
 }
 
+// locateSegments(h, docs, pos, refSeq|null, client|null) / locateUids(h, docs, uids, refSeq|null,
+// client|null) -> Int32Array, 12 words per query: the mt_seg_hit records of mt_locate_segments /
+// mt_locate_uids (row, uid, position, offset, local position, length, seq, client, removed seq,
+// removed client, marker refType, flags).  resolveRemotePositions(h, docs, pos, refSeq, client) ->
+// Int32Array [n] (mt_resolve_remote_positions; -1: undefined).  docs: Uint32Array; the others
+// Int32Arrays (uids: Uint32Array) with one entry per query; refSeq and client null: the observer
+// view.
+napi_value locate(napi_env env, napi_callback_info info, int mode) {
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return nullptr;
+    Handle *hd = get_handle(env, argv[0]);
+    if (!hd) return nullptr;
+    void *ptrs[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t lens[4] = {0, 0, 0, 0};
+    const napi_typedarray_type want[4] = {napi_uint32_array, mode == 1 ? napi_uint32_array : napi_int32_array,
+                                          napi_int32_array, napi_int32_array};
+    for (int i = 0; i < 4; i++) {
+        napi_valuetype vt;
+        NAPI_CALL(env, napi_typeof(env, argv[1 + i], &vt));
+        if (i >= 2 && (vt == napi_null || vt == napi_undefined)) continue;
+        napi_typedarray_type t;
+        napi_value ab;
+        size_t off;
+        if (napi_get_typedarray_info(env, argv[1 + i], &t, &lens[i], &ptrs[i], &ab, &off) != napi_ok || t != want[i]) {
+            napi_throw_type_error(env, nullptr, "locate: docs (and uids) are Uint32Arrays, pos, refSeq and client Int32Arrays");
+            return nullptr;
+        }
+        if (!ptrs[i]) ptrs[i] = &lens[i];   // (an empty array: any non-null pointer, never read)
+    }
+    const size_t n = lens[0];
+    if (lens[1] != n || (ptrs[2] && lens[2] != n) || (ptrs[3] && lens[3] != n) || (ptrs[2] == nullptr) != (ptrs[3] == nullptr)) {
+        napi_throw_range_error(env, nullptr, "locate: one entry per query; refSeq and client come together");
+        return nullptr;
+    }
+    const size_t words = mode == 2 ? n : n * (sizeof(mt_seg_hit) / 4);
+    void *d;
+    napi_value ab, arr;
+    NAPI_CALL(env, napi_create_arraybuffer(env, std::max<size_t>(words, 1) * 4, &d, &ab));
+    const uint32_t *docs = (const uint32_t *)ptrs[0];
+    const int32_t *ref = (const int32_t *)ptrs[2], *cli = (const int32_t *)ptrs[3];
+    int rc;
+    const char *what;
+    if (mode == 0)
+        rc = mt_locate_segments(hd->h, (uint32_t)n, docs, (const int32_t *)ptrs[1], ref, cli, (mt_seg_hit *)d), what = "mt_locate_segments";
+    else if (mode == 1)
+        rc = mt_locate_uids(hd->h, (uint32_t)n, docs, (const uint32_t *)ptrs[1], ref, cli, (mt_seg_hit *)d), what = "mt_locate_uids";
+    else
+        rc = mt_resolve_remote_positions(hd->h, (uint32_t)n, docs, (const int32_t *)ptrs[1], ref, cli, (int32_t *)d),
+        what = "mt_resolve_remote_positions";
+    if (rc) return throw_rc(env, hd, rc, what);
+    NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, words, ab, 0, &arr));
+    return arr;
+}
+napi_value LocateSegments(napi_env env, napi_callback_info info) { return locate(env, info, 0); }
+napi_value LocateUids(napi_env env, napi_callback_info info) { return locate(env, info, 1); }
+napi_value ResolveRemotePositions(napi_env env, napi_callback_info info) { return locate(env, info, 2); }
+
 // getDeltaLog(h, doc) -> Int32Array (only with deltaLogCapacity > 0; oracle layout)
 napi_value GetDeltaLog(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -900,7 +957,8 @@ napi_value Init(napi_env env, napi_value exports) {
                {"regeneratePending", RegeneratePending}, {"decodeSummaries", DecodeSummaries},
                {"applyOpsAsync", ApplyOpsAsync},         {"getContainingSegment", GetContainingSegment},
                {"getSegmentByUid", GetSegmentByUid},     {"getViewLengths", GetViewLengths},
-               {"extractSnapshots", ExtractSnapshots}};
+               {"extractSnapshots", ExtractSnapshots},   {"locateSegments", LocateSegments},
+               {"locateUids", LocateUids},               {"resolveRemotePositions", ResolveRemotePositions}};
     for (auto &f : fns) {
         napi_value v;
         NAPI_CALL(env, napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v));

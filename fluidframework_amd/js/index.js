@@ -334,6 +334,59 @@ class GpuMergeTreeBatch {
         return runs.map((r) => (r.length ? r[0].props : undefined));
     }
 
+    /**
+     * MergeTree.getContainingSegment for many cursors in one launch (mt_locate_segments).
+     * queries: [{doc, pos, refSeq?, clientId?}] with short client ids; refSeq / clientId omitted
+     * in every query: the observer view.  Per query undefined when no segment holds the position,
+     * else {uid, row, offset, position (in the queried view), localPosition (in the observer
+     * view), length, seq, clientId, removedSeq?, removedClientId?, markerRefType (undefined: a
+     * TextSegment), hostPath (answered by the single-query code: include/mt_replay.h)}.  The
+     * segments' text and ordinals come from the single-query calls and getTexts.
+     */
+    getContainingSegments(queries) { return this._locate(queries, "pos", native.locateSegments, Int32Array); }
+
+    /**
+     * MergeTree.getPosition for many (doc, uid, view) in one launch (mt_locate_uids): uid is a
+     * segment's device id (a delta-log entry's, or an earlier read-out's).  Records as
+     * getContainingSegments' with offset 0; undefined once the segment left the tree.
+     */
+    getPositions(queries) { return this._locate(queries, "uid", native.locateUids, Uint32Array); }
+
+    _views(queries) {
+        const remote = queries.some((q) => q.clientId !== undefined && q.clientId !== null);
+        return [Uint32Array.from(queries, (q) => q.doc),
+            remote ? Int32Array.from(queries, (q) => q.refSeq || 0) : null,
+            remote ? Int32Array.from(queries, (q) => q.clientId || 0) : null];
+    }
+
+    _locate(queries, key, fn, Keys) {
+        this.flush();
+        const [docs, ref, cli] = this._views(queries);
+        const w = fn(this.h, docs, Keys.from(queries, (q) => q[key]), ref, cli);
+        const out = [];
+        for (let q = 0, o = 0; q < queries.length; q++, o += 12) {
+            if (w[o] < 0) { out.push(undefined); continue; }
+            const r = { row: w[o], uid: w[o + 1] >>> 0, position: w[o + 2], offset: w[o + 3], localPosition: w[o + 4],
+                length: w[o + 5], seq: w[o + 6], clientId: w[o + 7],
+                markerRefType: w[o + 10] >= 0 ? w[o + 10] : undefined, hostPath: (w[o + 11] & 1) !== 0 };
+            if (w[o + 8] !== -2147483648) { r.removedSeq = w[o + 8]; r.removedClientId = w[o + 9]; }
+            out.push(r);
+        }
+        return out;
+    }
+
+    /**
+     * MergeTree.resolveRemoteClientPosition for many [{doc, pos, refSeq, clientId}] in one launch
+     * (mt_resolve_remote_positions): the sender's position in the observer view; undefined where
+     * the reference returns none.
+     */
+    resolveRemoteClientPositions(queries) {
+        this.flush();
+        const [docs, ref, cli] = this._views(queries);
+        const r = native.resolveRemotePositions(this.h, docs, Int32Array.from(queries, (q) => q.pos), ref, cli);
+        return Array.from(r, (p) => (p < 0 ? undefined : p));
+    }
+
     _recordProps(records, base, rec) {
         if (rec === 0xFFFFFFFF) { return undefined; }
         const at = base + rec, n = records[at];
@@ -693,6 +746,18 @@ class GpuClient {
     /** Client.getContainingSegment(pos) (client.ts:1006-1009, mergeTree.ts:1656-1667). */
     getContainingSegment(pos) {
         return this.mergeTree.getContainingSegment(pos, this.currentSeq, 0);
+    }
+
+    /**
+     * MergeTree.resolveRemoteClientPosition(remoteClientPosition, remoteClientRefSeq,
+     * remoteClientId) (mergeTree.ts:2140-2160; SharedSegmentSequence.resolveRemoteClientPosition,
+     * sequence.ts:310): a remote client's position in this replica's view, clientId a short id
+     * (getShortClientId); undefined where the reference returns none.
+     */
+    resolveRemoteClientPosition(remoteClientPosition, remoteClientRefSeq, remoteClientId) {
+        this._sync();
+        return this.batch.resolveRemoteClientPositions([{ doc: this.doc, pos: remoteClientPosition,
+            refSeq: remoteClientRefSeq, clientId: remoteClientId }])[0];
     }
 
     /** Client.getShortClientId / getLongClientId (client.ts:637-661): the observer is 0. */

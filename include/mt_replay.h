@@ -425,6 +425,59 @@ int mt_get_segment_by_uid(mt_handle *h, uint32_t doc, uint32_t uid, int32_t ref_
    client) queries: the root's partial length in each view. */
 int mt_get_view_lengths(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *ref_seq,
                         const int32_t *client, int32_t *out);
+/* ---- bulk segment read-outs: the three calls above for n (doc, ..., ref_seq, client) queries in
+        one launch, one wave per query walking the document's rows on the device (no copy of the
+        document).  Arguments and errors are mt_get_texts': the call settles the handle first; the
+        same document may appear in many queries, in any order; docs NULL: documents 0..n-1
+        (n <= n_docs); a doc >= n_docs or a pos < 0 is MT_E_INVALID, checked before anything is
+        launched; failed documents answer from the state they stopped in.  ref_seq and client may
+        both be NULL: the observer view for every query (client 0 is the observer view whatever
+        the ref_seq).  A remote view whose ref_seq lies outside its document's [minSeq, currentSeq]
+        makes the call return MT_E_INVALID (mt_last_error names the first such query).
+        In a remote view the device answers from prefix sums of the leaves' view lengths, which
+        is what the reference's tree gives whenever no segment of positive length is removed but
+        not inserted in the view; a query of any other view is answered by
+        the host code of the single-query calls (its document fetched once per call) and its
+        record carries MT_HIT_HOST. ---- */
+#define MT_HIT_HOST 1u           /* mt_seg_hit.flags: answered by the host path */
+typedef struct mt_seg_hit {      /* 48 bytes, one per query */
+    int32_t row;                 /* index in document order; -1: no such segment */
+    uint32_t uid;
+    int32_t position;            /* getPosition in the queried view */
+    int32_t offset;              /* mt_locate_segments: pos - position; mt_locate_uids: 0 */
+    int32_t local_position;      /* getPosition in the observer view (client 0) */
+    int32_t length;              /* the fields of mt_seg_info (seq / removed_seq -1: unassigned;
+                                    removed_client MT_RSEQ_NONE: not removed; marker_ref_type -1:
+                                    text); text and ordinals are not part of the bulk record */
+    int32_t seq, client, removed_seq, removed_client, marker_ref_type;
+    uint32_t flags;              /* MT_HIT_* */
+} mt_seg_hit;
+/* MergeTree.getContainingSegment(pos[q], ref_seq[q], client[q]) of document docs[q]. */
+int mt_locate_segments(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *pos, const int32_t *ref_seq,
+                       const int32_t *client, mt_seg_hit *out);
+/* MergeTree.getPosition of the segment with id uids[q] (row -1 once it left the tree). */
+int mt_locate_uids(mt_handle *h, uint32_t n, const uint32_t *docs, const uint32_t *uids, const int32_t *ref_seq,
+                   const int32_t *client, mt_seg_hit *out);
+/* The same with out (mt_seg_hit[n]) in device memory on the handle's device; the query arrays
+   stay host arrays.  The call returns once the records are written (host-path ones included). */
+int mt_locate_segments_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *pos,
+                              const int32_t *ref_seq, const int32_t *client, void *out_dev);
+int mt_locate_uids_device(mt_handle *h, uint32_t n, const uint32_t *docs, const uint32_t *uids,
+                          const int32_t *ref_seq, const int32_t *client, void *out_dev);
+/* MergeTree.getLength(ref_seq[q], client[q]) (mt_get_view_lengths) summed on the device: exact
+   in every view, no host path. */
+int mt_get_view_lengths_bulk(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *ref_seq,
+                             const int32_t *client, int32_t *out);
+/* MergeTree.resolveRemoteClientPosition(pos, ref_seq, client) (MT/mergeTree.ts:2140-2160): the
+   containing segment in the sender's view gives its observer position + offset; no segment and
+   pos equal to the view's length gives the observer length; anything else -1 (undefined). */
+int mt_resolve_remote_positions(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *pos,
+                                const int32_t *ref_seq, const int32_t *client, int32_t *out);
+/* The most recent bulk segment read-out: out[2] = {queries, of them answered by the host path};
+   *ms (nullable) its kernel's device time (HIP events).  Environment MT_LOCATE_ROW_WALK=1 makes
+   observer-view queries walk every row instead of skipping pages by their observer lengths and
+   the uid map (the A/B of tools/cursor_probe.py; results are identical). */
+int mt_last_locate(mt_handle *h, int64_t *out /* [2] */, float *ms);
 /* Debug: raw segment records (8 u32 per segment: segA then segB) and the 32-word header. */
 int mt_debug_raw(mt_handle *h, uint32_t doc, uint32_t *rows, uint32_t cap_rows, uint32_t *n_rows,
                  int32_t *hdr_words);

@@ -476,6 +476,14 @@ class MergeTreeBatch:
         self._check(self.lib.mt_last_zamboni_packs(self.h, _native.ptr(packs)), "mt_last_zamboni_packs")
         return {"in_place": int(out[0]), "fallback": int(out[1]), "in_place_packs": int(packs[0])}
 
+    def last_range_paths(self):
+        """The last batch's / generation's remove and annotate messages on paged documents by
+        path (mt_last_range_paths): one_page took the single-page path to its end, split_fallback
+        entered it and left it for a pending page split, general went the general way from the start."""
+        out = np.zeros(3, dtype=np.uint32)
+        self._check(self.lib.mt_last_range_paths(self.h, _native.ptr(out)), "mt_last_range_paths")
+        return {"one_page": int(out[0]), "split_fallback": int(out[1]), "general": int(out[2])}
+
     def last_grown(self):
         """The last batch's growth step (mt_last_grown): documents moved to larger paged
         capacities, rounds, documents in the big region and its capacities."""

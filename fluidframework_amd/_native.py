@@ -93,6 +93,7 @@ SIGNATURES = [
     ("mt_last_paged_peaks", _I, [_P, _P]),
     ("mt_last_zamboni", _I, [_P, _P]),
     ("mt_last_zamboni_packs", _I, [_P, _P]),
+    ("mt_last_range_paths", _I, [_P, _P]),
     ("mt_last_grown", _I, [_P, _P]),
     ("mt_generate", _P, [_P, _P, _U32, _P]),
     ("mt_generate_docs", _P, [_P, _P, _U32, _P, _P, _P]),

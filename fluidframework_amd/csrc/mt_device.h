@@ -26,7 +26,7 @@
 #define MT_MAXN 8               // MaxNodesInBlock           MT/mergeTree.ts:333
 #define MT_HALF 4               // MaxNodesInBlock / 2       MT/mergeTree.ts:2510
 #define MT_GRAN 256             // TextSegmentGranularity    MT/mergeTree.ts:1093
-#define MT_STATS_WORDS 20       // DevState.stats (0..14 and 16..18 in use)
+#define MT_STATS_WORDS 24       // DevState.stats (0..14, 16..18 and 20..22 in use)
 #define MT_ZAMBONI 2            // zamboniSegmentsMaxCount   MT/mergeTree.ts:1095
 #define MT_KMAX 8               // max keys in one segment's property set
 #define MT_PREC (1 + 2 * MT_KMAX)
@@ -191,7 +191,9 @@ struct DevState {
     uint32_t *stats;          // [0]: documents replayed in the HBM tier by the last launch
                               // (MT_STATS_WORDS words; 16 / 17: zamboni's scours outside the
                               // window done in place / through the window, mt_last_zamboni;
-                              // 18: in-place scours that repacked their page)
+                              // 18: in-place scours that repacked their page; 20 / 21 / 22:
+                              // range messages that entered the single-page path / of those,
+                              // left it for a page split / general path, mt_last_range_paths)
     // paged layout (PP == 0: disabled)
     v4i *pgA;                 // [n_docs][PP][64]
     u64 *pgO;

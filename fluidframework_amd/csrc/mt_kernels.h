@@ -486,6 +486,11 @@ __device__ __forceinline__ void pg_peaks(const DevState &st, PagedDoc<T> &pd, in
             if (zf) atomicAdd(st.stats + 17, zf);
             if (zp) atomicAdd(st.stats + 18, zp);
         }
+        // remove / annotate messages by pg_op_range's path (mt_last_range_paths; r1 includes rs)
+        const uint32_t r1 = pg_zcount(pd)[3], rs = pg_zcount(pd)[4], rg = pg_zcount(pd)[5];
+        if (r1) atomicAdd(st.stats + 20, r1);
+        if (rs) atomicAdd(st.stats + 21, rs);
+        if (rg) atomicAdd(st.stats + 22, rg);
     }
 }
 // Replay of the documents flagged by the LDS tier (retry[doc]) in the paged layout: a

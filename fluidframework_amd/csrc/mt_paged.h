@@ -44,8 +44,8 @@
 template <class T> struct PagedDoc {
     DocT<T> w;    // window: one page staged in LDS (first member: see pdoc)
     DocT<T> up;   // levels >= 1 of the tree (level 1 = pages, counted in leaf blocks)
-    LDS_AS PageMeta *meta;    // [PP] by page id (T::kHM: null -- gmeta instead); three counters
-                              // follow it (pg_zcount)
+    LDS_AS PageMeta *meta;    // [PP] by page id (T::kHM: null -- gmeta instead); six counters
+                              // follow it (pg_zcount; T::kHM: they follow sob)
     GLB_AS PageMeta *gmeta;   // T::kHM: the page metadata in HBM, where it lives for the launch
                               // (observer length, leaf-block counts, needsScour flags)
     LDS_AS int *pvl;          // [PP] by level-1 position: view length in the cached view (vr, vc)
@@ -142,10 +142,11 @@ static __host__ __device__ inline PagedLayout paged_layout(int PP, int PH, int U
     o = (o + 7u) & ~7u;
     L.offUO = o; o += packed ? 8u * MT_PK_MASKS + MT_PK_MASKS / 8 : ((((uint32_t)ob * UT) + 7u) & ~7u);
     L.offHeap = o; o += 8u * (PH + 1);
-    // (+ 12: the document's in-place / window scour and in-place pack counts, pg_zcount)
-    L.offMeta = o; o += hm ? 0u : (uint32_t)sizeof(PageMeta) * PP + 12u;
+    // (+ 24: the document's in-place / window scour and in-place pack counts, and its range
+    // messages by path -- pg_zcount; hm: behind sob)
+    L.offMeta = o; o += hm ? 0u : (uint32_t)sizeof(PageMeta) * PP + 24u;
     L.offUpage = o; o += packed ? 0u : (2u * UT + 3u) & ~3u;
-    L.offCob = o; o += hm ? 8u * (uint32_t)((PP + 63) / 64) + 4u * 64 : 4u * PP;   // cob + cdl + sob, or pvl
+    L.offCob = o; o += hm ? 8u * (uint32_t)((PP + 63) / 64) + 4u * 64 + 24u : 4u * PP;   // cob + cdl + sob (+ pg_zcount), or pvl
     L.offWscr = o; o += 64u * 4;
     L.offWnb = o; o += MT_LV * 4;
     L.offUnb = o; o += MT_LV * 4;
@@ -1605,9 +1606,17 @@ TD void pg_pack1_impl(PagedDoc<T> &pd, int pos) {
 // page exactly as HBM holds it.
 // The document's counts of zamboni's scours outside the window: [0] done in place, [1] through
 // the window after all (mt_last_zamboni), [2] those of [0] that repacked their page
-// (pg_pack_inplace, mt_last_zamboni_packs).  In LDS behind the page metadata: two more uniform
-// registers through the op loop cost P_C3 32 spilled VGPRs (tools/regs.sh).
-TD LDS_AS uint32_t *pg_zcount(PagedDoc<T> &pd) { return (LDS_AS uint32_t *)(pd.meta + pd.PP); }
+// (pg_pack_inplace, mt_last_zamboni_packs); and of its remove / annotate messages by the path
+// pg_op_range took: [3] entered the single-page path, [4] those of [3] that left it for a pending
+// page split (each counted where it is decided: mt_last_range_paths reports [3] - [4] as
+// one_page; the increment at the path's end cost 0.6 % of a C3 step, profiles/r11/not_kept.log),
+// [5] the general path from the start.  In LDS behind the page metadata (T::kHM, which keeps
+// none in LDS: behind sob): two more uniform registers through the op loop cost P_C3 32 spilled
+// VGPRs (tools/regs.sh).
+TD LDS_AS uint32_t *pg_zcount(PagedDoc<T> &pd) {
+    if constexpr (T::kHM) return (LDS_AS uint32_t *)(pd.sob + 64);
+    return (LDS_AS uint32_t *)(pd.meta + pd.PP);
+}
 template <class T> constexpr bool pg_zinplace() {
 #ifdef MT_NO_ZINPLACE
     return false;
@@ -2034,6 +2043,46 @@ TD void pg_boundary(PagedDoc<T> &pd, int p, int r, int c) {
     pg_win_sync(pd);
 }
 
+// The single-page path of pg_op_range: tiers that keep pvl by position and run neither the delta
+// log nor live documents (-DMT_NO_RANGE1 compiles it out: same-tree A/B).
+template <class T> constexpr bool pg_range1() {
+#ifdef MT_NO_RANGE1
+    return false;
+#else
+    return !T::kLog && !T::kHM && !T::kLive;
+#endif
+}
+// markRangeRemoved / annotateRange over the pages: a split at each end in a walk of its own
+// (pg_boundary), then the marking pass page by page.
+//
+// Single-page path (pg_range1).  Half of C3's messages are range ops a few units long, and
+// nearly all of them lie inside one page: p1 and p2 fall strictly inside the view span of the
+// position the first search finds.  The general path then searches three times for the same
+// position and syncs the page's metadata three times, and nothing reads what the first two
+// syncs write: boundary and range_mark work on the window's own rows and counts, a boundary
+// split changes neither the page's observer length nor any view length (pg_views_cached relies
+// on that), and the last sync overwrites blocks, counts and observer length from the same
+// window.  So: one search, the page staged once, both splits, the marking pass, one sync --
+// ids are created in today's order (the p1 split, then the p2 split), and tdirty / vvalid /
+// dirty end as the general path leaves them.  p2 at the page's view end is not taken: the
+// general marking loop moves on to the next page there (zero-length rows at its head).  Nor is
+// a range with p2 <= p1 (remote ranges are not validated): the general path splits at p2 in
+// whatever page holds it, possibly an earlier one, and touches nothing for p1 == p2 at a
+// page's first unit; start <= p1 < p2 < the page's view end is what makes the three searches
+// one.
+// Leaving the path: a split that gives the page its eighth leaf block (pend_split) is resolved
+// at once by a sync (pg_split_page), as pg_boundary does, and the general path goes on from the
+// step after that split -- it searches again, the directory has changed.
+// Compactions: whatever writes the window back or walks the pages from HBM must see the
+// metadata of the rows as they are.  From range_mark that is paged_props_compact alone
+// (ovf_mark fails when its arena is full, pg_ovf_compact and the text compaction run between
+// messages or from an insert; the heap is LDS).  A window is one wave of rows, so range_mark
+// asks props_ensure(w, MT_WAVE) exactly once, before it touches a row, and props_ensure
+// compacts exactly when props_top + MT_WAVE > P_cap: when a boundary split has left the
+// metadata behind and that holds, the sync runs before range_mark (the general path's order).
+// Syncing inside the compaction instead would also run for its other callers, whose window may
+// carry scour flags the metadata does not have yet (paged_props_compact's own note); this way
+// they are untouched and the common message pays two scalar compares.
 TD void pg_op_range(PagedDoc<T> &pd, const mt_op_rec &op, const GLB_AS uint32_t *pin) {
     DocT<T> &w = pd.w;
     const int r = op.ref_seq, c = op_cli(op), p1 = op.pos1, p2 = op.pos2;
@@ -2044,10 +2093,63 @@ TD void pg_op_range(PagedDoc<T> &pd, const mt_op_rec &op, const GLB_AS uint32_t 
         return;
     }
     if (!rec) rec = (const GLB_AS uint32_t *)&kEmptyPropsRec;
-    pg_boundary(pd, p1, r, c);
-    if (w.status) return;
-    pg_boundary(pd, p2, r, c);
-    if (w.status) return;
+    int step = 0;   // general path: next step (0: the p1 split, 1: the p2 split, 2: the marks)
+    if constexpr (pg_range1<T>()) {
+        pg_views_cached(pd, r, c);
+        if (w.status) return;
+        int start;
+        int ostart;
+        const int pos = pg_find(pd, p1, true, start, ostart);
+        if (pos >= 0 && p1 < p2 && p2 < start + uni(pd.pvl[pos])) {
+            if (lane() == 0) pg_zcount(pd)[3]++;
+            pg_load_pos(pd, pos, ostart);
+            if (w.status) return;
+            pd.tdirty = 1;
+            const int n0 = w.n;
+            if (start < p1) {
+                boundary(w, p1 - start, r, c);
+                if (w.status) return;
+                if (w.pend_split) step = 1;
+            }
+            if (step == 0) {
+                boundary(w, p2 - start, r, c);
+                if (w.status) return;
+                if (w.pend_split) step = 2;
+            }
+            if (step == 0) {
+                if (w.n != n0 && !rem && w.props_top + MT_WAVE > w.P_cap) {
+                    pg_win_sync(pd);   // paged_props_compact runs inside range_mark
+                    if (w.status) return;
+                }
+                Cb cb = cb_begin(w, op.seq, op.kind);
+                pd.vvalid = 0;   // range_mark changes view lengths
+                int carry = start, ocarry = ostart;
+                PG_T0(45)
+                range_mark(w, op, rec, carry, ocarry, cb);
+                PG_T1(45)
+                if (w.status) return;
+                pg_win_sync(pd);
+                if (w.status) return;
+                cb_end(w, cb);
+                return;
+            }
+            if (lane() == 0) pg_zcount(pd)[4]++;
+            pg_win_sync(pd);   // the page split
+            if (w.status) return;
+        } else {
+            if (lane() == 0) pg_zcount(pd)[5]++;
+        }
+    } else {
+        if (lane() == 0) pg_zcount(pd)[5]++;
+    }
+    if (step < 1) {
+        pg_boundary(pd, p1, r, c);
+        if (w.status) return;
+    }
+    if (step < 2) {
+        pg_boundary(pd, p2, r, c);
+        if (w.status) return;
+    }
     Cb cb = cb_begin(w, op.seq, op.kind);
     pg_views_cached(pd, r, c);
     if (w.status) return;
@@ -2864,9 +2966,7 @@ TD void pg_setup(PagedDoc<T> &pd, const DevState &st, int doc, LDS_AS uint8_t *s
     pd.zuid = 0;
     pd.zpv = 0;
     pd.press = 0;
-    if constexpr (!T::kHM) {
-        if (lane() == 0) pg_zcount(pd)[0] = pg_zcount(pd)[1] = pg_zcount(pd)[2] = 0;
-    }
+    if (lane() < 6) pg_zcount(pd)[lane()] = 0;
     pd.ovf_top = MT_OVF_HDR;
     pd.ovf_last = 0;
     pd.ovf_maxn = 0;

@@ -2408,6 +2408,15 @@ int mt_last_zamboni_packs(mt_handle *h, uint32_t *out) {
     return 0;
 }
 
+int mt_last_range_paths(mt_handle *h, uint32_t *out) {
+    if (!h || !out) return MT_E_INVALID;
+    HIPCHK(h, hipSetDevice(h->device));
+    SETTLE(h);
+    HIPCHK(h, hipMemcpy(out, h->st.stats + 20, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    out[0] -= out[1];   // the device counts entries into the path; those that left it are out[1]
+    return 0;
+}
+
 int mt_apply_ops(mt_handle *h, const int64_t *doc_op_off, const mt_op_rec *ops, uint64_t n_ops,
                  const uint16_t *text, uint64_t text_len, const uint32_t *props,
                  uint64_t props_len) {

@@ -251,6 +251,14 @@ int mt_last_zamboni(mt_handle *h, uint32_t *out);
    pack's scours and its regrouping on the page in HBM; a pack that goes on to level 1, a join
    above the append granularity or a text compaction still takes the window). */
 int mt_last_zamboni_packs(mt_handle *h, uint32_t *out);
+/* The remove and annotate messages of the most recent batch (or generation) applied to paged
+   documents, by the way they took: out[3] = {single-page path (both ends strictly inside one
+   page's view span: one page search, one metadata sync), those that entered it and left it for
+   the general path because a boundary split gave the page its eighth leaf block, general path
+   from the start}; every such message is in exactly one of the three.  Ranges with
+   pos2 <= pos1, and tiers with a delta log, live documents or their page metadata in HBM,
+   always take the general path. */
+int mt_last_range_paths(mt_handle *h, uint32_t out[3]);
 
 /* Growth step of the most recent batch (mt_sync runs it; see mt_options: the paged
    capacities are where documents start, not a limit): out[6] = {documents handed to it,

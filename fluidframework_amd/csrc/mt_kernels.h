@@ -772,14 +772,18 @@ __global__ void __launch_bounds__(MT_WAVE) k_generate_paged(DevState st, mt_gen_
 }
 
 // A summary header staged by k_load_header (LoadScratch) becomes a paged document at the
-// handle's full paged capacities (pg_convert from the staging buffers); the body appends
-// then replay like any paged document's messages.
+// handle's full paged capacities (pg_convert from the staging buffers), or, when it does not
+// fit them, at the big region's (kBig); the body appends then replay like any paged
+// document's messages.
 template <class T>
 __global__ void __launch_bounds__(MT_WAVE) k_load_convert(DevState st, LoadScratch sc, PagedCaps pc, int lo) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
     LDS_AS uint8_t *smem = (LDS_AS uint8_t *)smem_raw;
     const int r = blockIdx.x, doc = lo + r;   // summary r of the set -> document lo + r
-    if (doc >= st.n_docs || sc.off[2 * r] < 0 || st.hdr[doc].status) return;
+    if (doc >= st.n_docs || sc.off[2 * r] < 0 || st.hdr[doc].status || st.hdr[doc].pad[HDR_PAGED]) return;
+    // a header that outgrows the handle's capacities is paged in the growth step's big region by
+    // the kBig instantiation (mt_replay.hip load_grow); the first launch serves the others
+    if ((st.bslot != nullptr && st.bslot[doc] >= 0) != T::kBig) return;
     const PagedLayout L = paged_layout(pc.PP, pc.PH, pc.UT, 0, (int)sizeof(typename T::O_v));
     PagedDoc<T> pd;
     pg_setup(pd, st, doc, smem, L, pc);

@@ -341,9 +341,12 @@ __global__ void __launch_bounds__(MT_WAVE) k_extract(DevState st, int mode, int6
             const v4u b = uni4(Bv[i]);
             const int seq = a.y, rseq = a.z;
             const bool removed = rseq != MT_RSEQ_NONE;
-            if (seq == -1 || (removed && rseq <= ms)) continue;            // :189-191
+            // :189-191.  A live handle holds UnassignedSequenceNumber as MT_LOCAL_BASE + localSeq
+            // (mt_device.h): an unacked insert and a segment whose removal is pending are elided
+            // (-1 <= minSeq always holds); observer handles hold neither
+            if (seq == -1 || is_local_seq(seq) || (removed && (is_local_seq(rseq) || rseq <= ms))) continue;
             const bool marker = (b.z & MT_MARKER_BIT) != 0;
-            if (seq <= ms && (!removed || rseq == -1)) {                   // :196-215 coalesce
+            if (seq <= ms && !removed) {                                   // :196-215 coalesce
                 const bool nl = !marker && a.x > 0 && tb[b.x + a.x - 1] == '\n';
                 const bool can = open && !p_marker && !marker && !p_nl &&
                                  (p_len <= MT_GRAN || a.x <= MT_GRAN) && props_equal_set(pr, p_props, b.y);
@@ -1983,6 +1986,36 @@ static int regrow(mt_handle *h, const std::vector<uint32_t> &moving, const Paged
     return 0;
 }
 
+// The growth step's next capacities (grow_loop for replayed documents, load_grow for staged
+// summary headers): c doubled where the documents ran out (t: the unsettled table, hp: the
+// heap, pg: the pages), one capacity at a time while one paged launch can stage the layout in LDS
+static PagedCaps grown_caps(const PagedCaps &c, bool t, bool hp, bool pg) {
+    auto fits = [](const PagedCaps &q) { return paged_layout(q.PP, q.PH, q.UT, 0, 8).total <= 160 * 1024; };
+    PagedCaps r = c, x = c;
+    if (t) x.UT = std::min(2 * x.UT, 1 << 20);
+    if (fits(x)) r = x;
+    x = r;
+    if (hp) x.PH = std::min(2 * x.PH, 1 << 20);
+    if (fits(x)) r = x;
+    x = r;
+    if (pg) x.PP = std::min(2 * x.PP, 65535);
+    if (fits(x)) r = x;
+    return r;
+}
+// ... never below the big region's, once there is one: its paged capacities, arenas (T, P), uid
+// map (U) and overflow arena (O)
+static void at_least_big(const mt_handle *h, PagedCaps &c, int &T, int &P, int &U, int &O) {
+    if (h->big_caps.PP <= 0) return;
+    c.PP = std::max(c.PP, h->big_caps.PP);
+    c.PH = std::max(c.PH, h->big_caps.PH);
+    c.UT = std::max(c.UT, h->big_caps.UT);
+    T = std::max(T, h->st.big.T);
+    P = std::max(P, h->st.big.P);
+    U = std::max(U, h->st.big.UM);
+    O = std::max(O, h->st.big.OA);
+}
+static bool same_caps(const PagedCaps &a, const PagedCaps &b) { return a.PP == b.PP && a.PH == b.PH && a.UT == b.UT; }
+
 // After the launches of batch b: re-tiers and replays the documents they handed to the
 // growth step until none is left (synchronous).
 static int grow_loop(mt_handle *h, const mt_batch *b) {
@@ -2034,26 +2067,7 @@ static int grow_loop(mt_handle *h, const mt_batch *b) {
         // the new capacities: doubled where the documents ran out, never below the big
         // region's, within the LDS one paged launch may stage
         const bool have = h->big_caps.PP > 0;
-        auto fits = [](const PagedCaps &c) { return paged_layout(c.PP, c.PH, c.UT, 0, 8).total <= 160 * 1024; };
-        auto same = [](const PagedCaps &a, const PagedCaps &b) { return a.PP == b.PP && a.PH == b.PH && a.UT == b.UT; };
-        auto doubled = [&](const PagedCaps &c) {   // c doubled where needed, one capacity at a time while it fits
-            PagedCaps r = c, x = c;
-            if (t) x.UT = std::min(2 * x.UT, 1 << 20);
-            if (fits(x)) r = x;
-            x = r;
-            if (hp) x.PH = std::min(2 * x.PH, 1 << 20);
-            if (fits(x)) r = x;
-            x = r;
-            if (pg) x.PP = std::min(2 * x.PP, 65535);
-            if (fits(x)) r = x;
-            return r;
-        };
-        PagedCaps nc = judged ? doubled(launched) : h->big_caps;   // (judged == 0: only marked documents)
-        if (have) {
-            nc.PP = std::max(nc.PP, h->big_caps.PP);
-            nc.PH = std::max(nc.PH, h->big_caps.PH);
-            nc.UT = std::max(nc.UT, h->big_caps.UT);
-        }
+        PagedCaps nc = judged ? grown_caps(launched, t, hp, pg) : h->big_caps;   // (judged == 0: only marked documents)
         // the text / property arenas and the uid map (HBM only): doubled when a document's live
         // text / records / segments fill more than half of them after a compaction
         const int lT = launched_big ? st.big.T : st.T, lP = launched_big ? st.big.P : st.P;
@@ -2062,16 +2076,11 @@ static int grow_loop(mt_handle *h, const mt_batch *b) {
         int nP = judged && pr ? (int)std::min<int64_t>(2LL * lP, 1 << 26) : lP;
         int nU = judged && um ? (int)std::min<int64_t>(2LL * lU, 1 << 24) : lU;
         int nO = judged && ov ? (int)std::min<int64_t>(2LL * lO, 1 << 30) : lO;
-        if (have) {
-            nT = std::max(nT, st.big.T);
-            nP = std::max(nP, st.big.P);
-            nU = std::max(nU, st.big.UM);
-            nO = std::max(nO, st.big.OA);
-        }
+        at_least_big(h, nc, nT, nP, nU, nO);
         int rc = 0;
         PagedCaps pc = nc;
         bool big = true;
-        if (same(nc, launched) && nT == lT && nP == lP && nU == lU && nO == lO) {
+        if (same_caps(nc, launched) && nT == lT && nP == lP && nU == lU && nO == lO) {
             // no LDS capacity can grow: the documents run to their end at the capacities they
             // were handed over at (in their own region) and fail as before the step existed
             // only if they do outgrow them -- the arenas and the uid map still grow
@@ -2081,7 +2090,7 @@ static int grow_loop(mt_handle *h, const mt_batch *b) {
         } else {
             bool all_big = have;
             for (uint32_t d : moving) all_big = all_big && !h->bslot_h.empty() && h->bslot_h[d] >= 0;
-            if (!(all_big && same(nc, h->big_caps) && nT == st.big.T && nP == st.big.P && nU == st.big.UM &&
+            if (!(all_big && same_caps(nc, h->big_caps) && nT == st.big.T && nP == st.big.P && nU == st.big.UM &&
                   nO == st.big.OA))
                 rc = regrow(h, moving, nc, nT, nP, nU, nO);
             pc.grow = 1;   // (the arenas can always grow; a round that raises nothing runs with grow 0)
@@ -2442,6 +2451,7 @@ struct mt_snapshots {
     // headers larger than the flat capacities on a paged handle (k_load_convert)
     LoadScratch sc = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int64_t *sc_off = nullptr;
+    std::vector<int64_t> sc_off_h;   // host copy of sc_off (load_grow)
     bool any_big = false;
 };
 
@@ -2522,6 +2532,7 @@ mt_snapshots *mt_snapshots_upload_range(mt_handle *h, uint32_t doc_lo, uint32_t 
                  hipMalloc(&s->sc_off, (size_t)N * 16) == hipSuccess &&
                  hipMemcpy(s->sc_off, so.data(), (size_t)N * 16, hipMemcpyHostToDevice) == hipSuccess;
             s->sc.off = s->sc_off;
+            s->sc_off_h = so;
         }
     }
     if (!ok) {
@@ -2625,6 +2636,56 @@ mt_snapshots *mt_snapshots_upload(mt_handle *h, const int64_t *doc_seg_off, cons
                                      props_len, min_seq, cur_seq);
 }
 
+// A staged header that does not fit the paged capacities it was converted at (pages, the
+// unsettled table: k_load_convert left it with MT_DOC_CAPACITY and the cause) is handed to the
+// growth step's big region, as a replayed document that outgrows them is (grow_loop): what ran
+// out is doubled, round after round, within the LDS one paged launch may stage, and
+// k_load_convert's kBig instantiation pages the header there.  Synchronous; reached only by
+// summary sets with staged headers.
+static int load_grow(mt_handle *h, const mt_snapshots *s) {
+    DevState &st = h->st;
+    const uint32_t N = s->n_docs;
+    std::vector<DocHdr> hdr(N);
+    PagedCaps cur = h->pg_full;
+    for (int round = 0; round < 16; round++) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(hdr.data(), st.hdr + s->doc_lo, (size_t)N * sizeof(DocHdr), hipMemcpyDeviceToHost));
+        std::vector<uint32_t> moving;
+        bool t = false, hp = false, pg = false;
+        for (uint32_t r = 0; r < N; r++) {
+            const DocHdr &x = hdr[r];
+            if (s->sc_off_h[2 * r] < 0 || x.status != MT_DOC_CAPACITY || x.pad[HDR_PAGED]) continue;
+            const int cause = x.pad[HDR_DIAG];
+            if (cause != 3 && cause != 7 && cause != 8) continue;   // (an arena, the uid map: not the paged capacities)
+            moving.push_back(s->doc_lo + r);
+            t = t || cause == 8;
+            hp = hp || cause == 3;
+            pg = pg || cause == 7;
+        }
+        if (moving.empty()) return 0;
+        PagedCaps nc = grown_caps(cur, t, hp, pg);
+        if (same_caps(nc, cur)) return 0;   // nothing can grow: they stay failed
+        int nT = st.T, nP = st.P, nU = st.UM, nO = st.OA;
+        at_least_big(h, nc, nT, nP, nU, nO);
+        const int rc = regrow(h, moving, nc, nT, nP, nU, nO);
+        if (rc) return rc;
+        for (uint32_t d : moving) {   // the header k_load_header wrote, without the failure
+            DocHdr &xh = hdr[d - s->doc_lo];
+            xh.status = 0;
+            xh.pad[HDR_DIAG] = 0;
+            HIPCHK(h, hipMemcpy(st.hdr + d, &xh, sizeof(DocHdr), hipMemcpyHostToDevice));
+        }
+        const PagedCaps pc = h->big_caps;
+        const size_t lb = paged_layout(pc.PP, pc.PH, pc.UT, 0, 8).total;
+        const void *k = h->ordinals ? MTK(LC_BIG_LOG) : MTK(LC_BIG_FAST);
+        if (lb > 64 * 1024) HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
+        launch_load_convert(k, dim3(N), dim3(MT_WAVE), lb, h->stream, h->st, s->sc, pc, (int)s->doc_lo);
+        HIPCHK(h, hipGetLastError());
+        cur = nc;
+    }
+    return 0;
+}
+
 int mt_snapshots_load_async(mt_handle *h, const mt_snapshots *s) {
     if (!h || !s || s->doc_lo > h->n_docs || s->n_docs > h->n_docs - s->doc_lo) return MT_E_INVALID;
     if (h->pending) SETTLE(h);
@@ -2652,6 +2713,12 @@ int mt_snapshots_load_async(mt_handle *h, const mt_snapshots *s) {
             launch_load_convert(MTK(LC_FAST), dim3(s->n_docs), dim3(MT_WAVE), lb, h->stream, h->st,
                                s->sc, pc, (int)s->doc_lo);
         HIPCHK(h, hipGetLastError());
+        const int rc = load_grow(h, s);
+        if (rc) {   // (the load's events stay a pair: mt_last_load_ms reads both)
+            (void)hipEventRecord(h->ev_load1, h->stream);
+            h->load_timed = true;
+            return rc;
+        }
     }
     HIPCHK(h, hipEventRecord(h->ev_load1, h->stream));
     h->load_timed = true;

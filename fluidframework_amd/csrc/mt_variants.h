@@ -34,7 +34,9 @@
     X(GP_NARROW, (k_generate_paged<TierPagedT<false, true>>))                        \
     X(GP_FULL, (k_generate_paged<TierPagedT<false>>))                                \
     X(LC_FAST, (k_load_convert<TierPagedT<false>>))                                  \
-    X(LC_LOG, (k_load_convert<TierPagedT<true>>))
+    X(LC_LOG, (k_load_convert<TierPagedT<true>>))                                    \
+    X(LC_BIG_FAST, (k_load_convert<TierPagedT<false, false, true>>))                 \
+    X(LC_BIG_LOG, (k_load_convert<TierPagedT<true, false, true>>))
 
 #define MT_VARIANT_DECL(n, k) const void *mtk_##n();
 MT_VARIANTS(MT_VARIANT_DECL)

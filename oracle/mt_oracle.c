@@ -1819,6 +1819,141 @@ fail:
     return -1;
 }
 
+/* ------------------------------------------------------------------ summary extraction */
+/* SnapshotV1.extractSync MT/snapshotV1.ts:156-252 over the segment list, written in the form
+   mt_extract_snapshots gives (include/mt_replay.h): one mt_seg_rec per pushed spec, the text
+   of every TextSegment spec appended to `text`, every property set as [n, (key, value) x n]
+   appended to `props`; offsets are relative to the document's own output.
+     - a coalesced or single below-MSN spec (pushSeg, :177-179): flags 0 (| MT_F_MARKER), seq 0,
+       client -2, removed_seq none;
+     - a spec with merge info (:222-241): MT_SEG_MERGE_INFO, and MT_SEG_HAS_SEQ with seq /
+       client when segment.seq > minSeq; removedSeq / removedClient when removedSeq is set.
+   Client ids are the short ids of the records the document was built from (mt_op_rec.client,
+   mt_seg_rec.client): the device stores the same ids, so they compare as they are; the seed's
+   LocalClientId (-1) and a loaded spec's NonCollabClient (-2) never reach a record (their seq
+   is 0, never above minSeq).  A property set's pairs come in the object's own key order (the
+   order the reference's JSON.stringify walks, integer-like keys aside); the device stores a
+   set in its own order, so device records are compared after sorting pairs by key id. */
+typedef struct ExtAcc {
+    orc_doc *d;
+    mt_seg_rec *recs;
+    uint16_t *text;
+    uint32_t *props;
+    int64_t nrec, ntext, nprop;
+    /* prev: the coalescing candidate (:181).  The clone + append chain (:208-209) is kept as
+       the record already written: its text grows in place, its properties are the first
+       segment's (TextSegment.clone copies them, MT/textSegment.ts:56-61) */
+    int have_prev, prev_marker, prev_nl;
+    int32_t prev_len;
+    const Props *prev_props;
+    int64_t prev_rec;
+} ExtAcc;
+
+static void ext_text(ExtAcc *a, const Seg *s) {
+    if (a->text && s->len > 0) memcpy(a->text + a->ntext, s->text, sizeof(uint16_t) * s->len);
+    a->ntext += s->len;
+}
+/* toJSONObject (MT/textSegment.ts:48-54, MT/mergeTree.ts:690-694) into a new record */
+static mt_seg_rec *ext_push(ExtAcc *a, const Seg *s) {
+    mt_seg_rec r;
+    memset(&r, 0, sizeof(r));
+    r.len = s->len;
+    r.seq = 0;
+    r.removed_seq = RSEQ_NONE;
+    r.client = -2;
+    r.props = MT_NO_PROPS;
+    if (s->marker >= 0) {
+        r.flags = MT_F_MARKER;
+        r.payload = (uint32_t)s->marker;
+    } else {
+        r.payload = (uint32_t)a->ntext;
+        ext_text(a, s);
+    }
+    if (s->props) {
+        r.props = (uint32_t)a->nprop;
+        if (a->props) {
+            uint32_t *o = a->props + a->nprop;
+            o[0] = (uint32_t)s->props->n;
+            for (int i = 0; i < s->props->n; i++) {
+                o[1 + 2 * i] = s->props->key[i];
+                o[2 + 2 * i] = s->props->val[i];
+            }
+        }
+        a->nprop += 1 + 2 * (int64_t)s->props->n;
+    }
+    mt_seg_rec *out = NULL;
+    if (a->recs) {
+        a->recs[a->nrec] = r;
+        out = &a->recs[a->nrec];
+    }
+    a->nrec++;
+    return out;
+}
+static void ext_fn(Seg *s, void *arg) {
+    ExtAcc *a = (ExtAcc *)arg;
+    const int32_t ms = a->d->min_seq;
+    /* :189 -- `undefined <= minSeq` is false; UnassignedSequenceNumber (-1) <= minSeq holds */
+    if (s->seq == UNASSIGNED || (s->rseq != RSEQ_NONE && s->rseq <= ms)) return;
+    if (s->seq <= ms && (s->rseq == RSEQ_NONE || s->rseq == UNASSIGNED)) {   /* :196-199 */
+        if (a->have_prev) {
+            /* prev.canAppend(segment): TextSegment :63-68, Marker :827-829 (never) */
+            const int can = !a->prev_marker && !a->prev_nl && s->marker < 0 &&
+                            (a->prev_len <= TEXT_GRANULARITY || s->len <= TEXT_GRANULARITY);
+            if (can && match_props(a->prev_props, s->props)) {               /* :205-209 */
+                ext_text(a, s);
+                a->prev_len += s->len;
+                if (s->len > 0) a->prev_nl = s->text[s->len - 1] == '\n';
+                if (a->recs) a->recs[a->prev_rec].len = a->prev_len;
+                return;
+            }
+        }
+        /* :202-204 / :213-214: the candidate's record is opened here and grows in place; the
+           reference pushes it when the next spec is pushed, which leaves the same order */
+        a->have_prev = 1;
+        a->prev_marker = s->marker >= 0;
+        a->prev_nl = s->marker < 0 && s->len > 0 && s->text[s->len - 1] == '\n';
+        a->prev_len = s->len;
+        a->prev_props = s->props;
+        a->prev_rec = a->nrec;
+        ext_push(a, s);
+        return;
+    }
+    a->have_prev = 0;                                                        /* :219-220 */
+    const int64_t at = a->nrec;
+    ext_push(a, s);
+    if (a->recs) {
+        mt_seg_rec *r = &a->recs[at];
+        r->flags |= MT_SEG_MERGE_INFO;
+        if (s->seq > ms) {                                                   /* :224-227 */
+            r->flags |= MT_SEG_HAS_SEQ;
+            r->seq = s->seq;
+            r->client = (int16_t)s->client;
+        }
+        if (s->rseq != RSEQ_NONE) {                                          /* :230-234 */
+            r->removed_seq = s->rseq;
+            r->removed_client = (int16_t)s->rclient;
+        }
+    }
+}
+/* counts = {records, text units, props words}; with recs == NULL only counted.  win (may be
+   NULL) = {minSeq, currentSeq} of the collab window (:158) */
+void orc_extract(orc_doc *d, int64_t *counts, mt_seg_rec *recs, uint16_t *text, uint32_t *props, int32_t *win) {
+    ExtAcc a;
+    memset(&a, 0, sizeof(a));
+    a.d = d;
+    a.recs = recs;
+    a.text = recs ? text : NULL;
+    a.props = recs ? props : NULL;
+    walk_segs(&d->root->n, ext_fn, &a);
+    counts[0] = a.nrec;
+    counts[1] = a.ntext;
+    counts[2] = a.nprop;
+    if (win) {
+        win[0] = d->min_seq;
+        win[1] = d->current_seq;
+    }
+}
+
 /* ------------------------------------------------------------------ batch replay */
 typedef struct BatchArg {
     int32_t d0, d1;
@@ -1831,6 +1966,14 @@ typedef struct BatchArg {
     const uint16_t *seed;
     mt_checksum *sum;
     int32_t *status;
+    /* orc_replay_extract_batch: at most op_limit records of each document (< 0: all), then
+       orc_extract -- counting into io (x_recs NULL) or writing at the offsets io holds */
+    int32_t op_limit;
+    int64_t *io;
+    mt_seg_rec *x_recs;
+    uint16_t *x_text;
+    uint32_t *x_props;
+    int32_t *x_win;
 } BatchArg;
 
 static void *batch_worker(void *p) {
@@ -1839,19 +1982,30 @@ static void *batch_worker(void *p) {
         const int32_t doc = __atomic_fetch_add(a->next, 1, __ATOMIC_RELAXED);
         if (doc >= a->d1) break;
         orc_doc *d = orc_new(a->seed + a->seed_off[doc], (int32_t)(a->seed_off[doc + 1] - a->seed_off[doc]));
-        for (int64_t i = a->doc_op_off[doc]; i < a->doc_op_off[doc + 1]; i++)
+        int64_t end = a->doc_op_off[doc + 1];
+        if (a->io && a->op_limit >= 0 && a->doc_op_off[doc] + a->op_limit < end) end = a->doc_op_off[doc] + a->op_limit;
+        for (int64_t i = a->doc_op_off[doc]; i < end; i++)
             if (orc_apply(d, &a->ops[i], a->text, a->props)) break;
         orc_checksum(d, &a->sum[doc]);
         a->status[doc] = d->status;
+        if (a->io) {
+            int64_t c[3];
+            int64_t *io = a->io + 3 * (int64_t)doc;
+            if (a->x_recs)
+                orc_extract(d, c, a->x_recs + io[0], a->x_text + io[1], a->x_props + io[2], a->x_win + 2 * doc);
+            else
+                orc_extract(d, io, NULL, NULL, NULL, a->x_win ? a->x_win + 2 * doc : NULL);
+        }
         orc_free(d);
     }
     return NULL;
 }
 
-int32_t orc_replay_batch(int32_t n_docs, const int64_t *doc_op_off, const mt_op_rec *ops,
-                         const uint16_t *text_arena, const uint32_t *props_arena,
-                         const int64_t *seed_off, const uint16_t *seed_arena,
-                         mt_checksum *out_sum, int32_t *out_status, int32_t threads) {
+static int32_t replay_batch_impl(int32_t n_docs, const int64_t *doc_op_off, const mt_op_rec *ops,
+                                 const uint16_t *text_arena, const uint32_t *props_arena,
+                                 const int64_t *seed_off, const uint16_t *seed_arena,
+                                 mt_checksum *out_sum, int32_t *out_status, int32_t threads,
+                                 const BatchArg *ext) {
     if (threads < 1) threads = 1;
     if (threads > n_docs) threads = n_docs > 0 ? n_docs : 1;
     pthread_t *th = (pthread_t *)calloc(threads, sizeof(pthread_t));
@@ -1870,12 +2024,45 @@ int32_t orc_replay_batch(int32_t n_docs, const int64_t *doc_op_off, const mt_op_
         a->seed = seed_arena;
         a->sum = out_sum;
         a->status = out_status;
+        if (ext) {
+            a->op_limit = ext->op_limit;
+            a->io = ext->io;
+            a->x_recs = ext->x_recs;
+            a->x_text = ext->x_text;
+            a->x_props = ext->x_props;
+            a->x_win = ext->x_win;
+        }
         pthread_create(&th[t], NULL, batch_worker, a);
     }
     for (int t = 0; t < threads; t++) pthread_join(th[t], NULL);
     free(th);
     free(args);
     return 0;
+}
+
+int32_t orc_replay_batch(int32_t n_docs, const int64_t *doc_op_off, const mt_op_rec *ops,
+                         const uint16_t *text_arena, const uint32_t *props_arena,
+                         const int64_t *seed_off, const uint16_t *seed_arena,
+                         mt_checksum *out_sum, int32_t *out_status, int32_t threads) {
+    return replay_batch_impl(n_docs, doc_op_off, ops, text_arena, props_arena, seed_off, seed_arena, out_sum,
+                             out_status, threads, NULL);
+}
+
+int32_t orc_replay_extract_batch(int32_t n_docs, const int64_t *doc_op_off, const mt_op_rec *ops,
+                                 const uint16_t *text_arena, const uint32_t *props_arena,
+                                 const int64_t *seed_off, const uint16_t *seed_arena, int32_t op_limit,
+                                 int64_t *io, mt_seg_rec *recs, uint16_t *text, uint32_t *props, int32_t *win,
+                                 mt_checksum *out_sum, int32_t *out_status, int32_t threads) {
+    BatchArg ext;
+    memset(&ext, 0, sizeof(ext));
+    ext.op_limit = op_limit;
+    ext.io = io;
+    ext.x_recs = recs;
+    ext.x_text = text;
+    ext.x_props = props;
+    ext.x_win = win;
+    return replay_batch_impl(n_docs, doc_op_off, ops, text_arena, props_arena, seed_off, seed_arena, out_sum,
+                             out_status, threads, &ext);
 }
 
 /* ------------------------------------------------------------------ batch load + replay (C5) */

@@ -85,6 +85,25 @@ int32_t orc_replay_batch(int32_t n_docs, const int64_t *doc_op_off, const mt_op_
                          const int64_t *seed_off, const uint16_t *seed_arena,
                          mt_checksum *out_sum, int32_t *out_status, int32_t threads);
 
+/* SnapshotV1.extractSync (MT/snapshotV1.ts:156-252) of the document -- an observer's, a loaded
+   replica's or a live participant's (unacked inserts and segments whose removal is pending
+   are elided, :189) -- in the form mt_extract_snapshots gives: counts = {records, text units,
+   props words}; recs == NULL only counts.  Record offsets are relative to the document's own
+   text / props output; win (may be NULL) = {minSeq, currentSeq}.
+   Client ids: the short ids of the records the document was built from (mt_op_rec.client /
+   mt_seg_rec.client), which are the ids the device stores -- they compare unchanged.
+   Property pairs: the object's own key order (what the reference serialises); the device
+   keeps its storage order, so compare device records after sorting pairs by key id. */
+void orc_extract(orc_doc *d, int64_t *counts, mt_seg_rec *recs, uint16_t *text, uint32_t *props, int32_t *win);
+/* orc_replay_batch, then orc_extract of every document: the first op_limit records of each
+   document only (< 0: all).  Two calls as mt_extract_snapshots: with recs == NULL io[3 * doc]
+   receives the counts; with the caller's prefix sums in io the outputs are written there. */
+int32_t orc_replay_extract_batch(int32_t n_docs, const int64_t *doc_op_off, const mt_op_rec *ops,
+                                 const uint16_t *text_arena, const uint32_t *props_arena,
+                                 const int64_t *seed_off, const uint16_t *seed_arena, int32_t op_limit,
+                                 int64_t *io, mt_seg_rec *recs, uint16_t *text, uint32_t *props, int32_t *win,
+                                 mt_checksum *out_sum, int32_t *out_status, int32_t threads);
+
 /* Config C5 on `threads` host threads: load each document's summary, replay its ops. */
 int32_t orc_load_replay_batch(int32_t n_docs, const int64_t *seg_off, const int32_t *n_header,
                               const mt_seg_rec *segs, const uint16_t *seg_text, const uint32_t *seg_props,

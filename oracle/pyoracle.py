@@ -76,6 +76,10 @@ def lib():
         L.orc_load_replay_batch.restype = i32
         L.orc_load.restype = P
         L.orc_load.argtypes = [P, i32, i32, P, P, i32, i32]
+        L.orc_extract.restype = None
+        L.orc_extract.argtypes = [P, P, P, P, P, P]
+        L.orc_replay_extract_batch.argtypes = [i32, P, P, P, P, P, P, i32, P, P, P, P, P, P, P, i32]
+        L.orc_replay_extract_batch.restype = i32
         _lib = L
     return _lib
 
@@ -171,6 +175,21 @@ class OracleDoc:
         lib().orc_containing(self.h, int(pos), int(ref_seq), int(client), _p(o))
         return None if o[0] < 0 else tuple(int(x) for x in o)
 
+    def extract(self):
+        """SnapshotV1.extractSync of the document (orc_extract) as extract_snapshots gives one:
+        dict(segs, text, props, min_seq, cur_seq); record offsets index text / props."""
+        from fluidframework_amd.snapshot import SEG_DTYPE
+        L = lib()
+        c = np.zeros(3, dtype=np.int64)
+        win = np.zeros(2, dtype=np.int32)
+        L.orc_extract(self.h, _p(c), None, None, None, None)
+        segs = np.zeros(max(int(c[0]), 1), dtype=SEG_DTYPE)
+        text = np.zeros(max(int(c[1]), 1), dtype=np.uint16)
+        props = np.zeros(max(int(c[2]), 1), dtype=np.uint32)
+        L.orc_extract(self.h, _p(c), _p(segs), _p(text), _p(props), _p(win))
+        return dict(segs=segs[:int(c[0])], text=text[:int(c[1])], props=props[:int(c[2])],
+                    min_seq=int(win[0]), cur_seq=int(win[1]))
+
     def outputs(self):
         L = lib()
         n = L.orc_text(self.h, None, 0)
@@ -228,6 +247,38 @@ def replay_batch(arrays, threads=1):
     lib().orc_replay_batch(n_docs, _p(a["doc_off"]), _p(a["ops"]), _p(a["text"]), _p(a["props"]),
                            _p(a["seed_off"]), _p(a["seed"]), _p(sums), _p(status), threads)
     return sums, status
+
+
+def replay_extract_batch(arrays, op_limit=-1, threads=1):
+    """replay_batch of the first `op_limit` records of every document (< 0: all), then
+    SnapshotV1.extractSync of each (orc_replay_extract_batch), in the layout of
+    MergeTreeBatch.extract_snapshots_raw: (counts[n_docs, 3], records, text, props, min_seq,
+    cur_seq), and the replay's (checksums, statuses)."""
+    from fluidframework_amd.snapshot import SEG_DTYPE
+    n_docs = len(arrays["doc_off"]) - 1
+    sums = np.zeros(n_docs, dtype=CHECKSUM_DTYPE)
+    status = np.zeros(n_docs, dtype=np.int32)
+    a = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    io = np.zeros(3 * n_docs, dtype=np.int64)
+    win = np.zeros(2 * n_docs, dtype=np.int32)
+
+    def call(recs, text, props):
+        lib().orc_replay_extract_batch(n_docs, _p(a["doc_off"]), _p(a["ops"]), _p(a["text"]), _p(a["props"]),
+                                       _p(a["seed_off"]), _p(a["seed"]), int(op_limit), _p(io),
+                                       None if recs is None else _p(recs), None if recs is None else _p(text),
+                                       None if recs is None else _p(props), _p(win), _p(sums), _p(status), threads)
+    call(None, None, None)
+    counts = io.reshape(-1, 3).copy()
+    tot = counts.sum(axis=0)
+    recs = np.zeros(max(int(tot[0]), 1), dtype=SEG_DTYPE)
+    text = np.zeros(max(int(tot[1]), 1), dtype=np.uint16)
+    props = np.zeros(max(int(tot[2]), 1), dtype=np.uint32)
+    off = np.zeros_like(counts)
+    off[1:] = np.cumsum(counts, axis=0)[:-1]
+    io[:] = off.reshape(-1)
+    call(recs, text, props)
+    w = win.reshape(-1, 2)
+    return (counts, recs[:int(tot[0])], text, props, w[:, 0].copy(), w[:, 1].copy()), (sums, status)
 
 
 def load_replay_batch(load, arrays, threads=1):

@@ -881,6 +881,18 @@ function liveDoc(cfg, doc) {
         unseq.push({ op, ref: c.getCurrentSeq(), sgs });
     };
     const trace = [];          // cfg.trace (debugging): the local text after every event
+    // cfg.snaps: the participant's own summary (SnapshotV1.extractSync + emit, chunk size
+    // cfg.chunk) just before every reconnect and once before the drain:
+    // [events so far, the local client's long id then, {path: contents}]
+    const snaps = [];
+    const takeSnap = () => {
+        const saved = c.mergeTree.options;
+        c.mergeTree.options = { ...(saved || {}), mergeTreeSnapshotChunkSize: cfg.chunk || 10000 };
+        const snap = new SnapshotV1(c.mergeTree, logger);
+        c.mergeTree.options = saved;
+        snap.extractSync();
+        snaps.push([events.length, localId, treeChunks(snap.emit())]);
+    };
     let maxDepth = 0;          // deepest segment-group queue of any segment (cfg.track_depth)
     for (let step = 0; step < cfg.steps; step++) {
         if (cfg.track_depth) {
@@ -944,6 +956,7 @@ function liveDoc(cfg, doc) {
             submit(op, before);
         } else if (u < frac(cfg.p_local + cfg.p_reconnect)) {
             if (unseq.length === 0) { continue; }
+            if (cfg.snaps) { takeSnap(); }
             localId = `local-${events.length}`;
             c.startOrUpdateCollaboration(localId);
             const old = unseq.splice(0, unseq.length);
@@ -996,6 +1009,7 @@ function liveDoc(cfg, doc) {
     out.pending = pendingGroups(c).length;
     out.localSeq = c.mergeTree.getCollabWindow().localSeq;
     if (cfg.track_depth) { out.maxGroupDepth = maxDepth; }
+    if (cfg.snaps) { takeSnap(); }
     // drain: the server sequences every op still unsequenced (their echoes ack them)
     const drain = [];
     while (unseq.length > 0) {
@@ -1011,7 +1025,9 @@ function liveDoc(cfg, doc) {
     drained.pending = pendingGroups(c).length;
     delete drained.deltas;
     delete drained.tree;
-    return { doc, seed_text: seedText, events, out, drain, drained };
+    const rec = { doc, seed_text: seedText, events, out, drain, drained };
+    if (cfg.snaps) { rec.snaps = snaps; }
+    return rec;
 }
 
 const [mode, ...rest] = process.argv.slice(2);

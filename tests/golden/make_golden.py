@@ -7,7 +7,7 @@ fixture holds, per document, the input op log (compact messages) and the referen
 outputs (text, length, property runs, leaf-block partition, segment table, every delta
 callback).  The fixtures are data, not reference source.
 
-    python3 tests/golden/make_golden.py [--snapshots | --farm | --errors | --rich | --events | --live |
+    python3 tests/golden/make_golden.py [--snapshots [emit] | --farm | --errors | --rich | --events | --live |
                                          --readouts-xl | --only name,name |
                                          --zamboni [name,name]]
 
@@ -102,7 +102,44 @@ def _dump(name, data):
         json.dump(data, fh, separators=(",", ":"))
 
 
-def make_snapshot_fixtures():
+# Emission only (tests/test_extract.py: the C restatement's extractSync against the summary the
+# reference wrote): longer and wider documents than SNAP_FIXTURES, header only (one chunk),
+# kept as {doc, seed_text, msgs, chunks}.  ref_snap_wide: 64 writers at lag 1000 -- most
+# segments are above the minimum sequence number and carry merge info.
+SNAP_EMIT_FIXTURES = {
+    "ref_snap_long": ("c3", dict(ops=4000, tail=0, chunk=1 << 30, settle="alternate"), 2),
+    "ref_snap_wide": ("c4", dict(ops=1500, tail=0, chunk=1 << 30, settle="alternate"), 4),
+}
+# Participant summaries (harness "live" with snaps: the participant's own extractSync + emit
+# just before every reconnect and before the drain): unacked inserts and pending removes are
+# elided (MT/snapshotV1.ts:189)
+LIVE_SNAP_FIXTURES = {
+    "ref_live_snap": (dict(seed=4949, steps=400, p_local=0.4, p_reconnect=0.02, p_ack=0.4, p_marker=0.05,
+                           snaps=1, chunk=10000), 3),
+}
+
+
+def make_snapshot_emit_fixtures():
+    configs = json.load(open(os.path.join(REPO, "bench", "configs.json")))
+    for name, (base, over, ndocs) in SNAP_EMIT_FIXTURES.items():
+        cfg = {k: v for k, v in configs[base].items() if not k.startswith("_") and k != "docs"}
+        cfg.update(over)
+        data = _harness("snap", cfg, 0, ndocs)
+        docs = [{k: d[k] for k in ("doc", "seed_text", "msgs", "chunks")} for d in data["docs"]]
+        _dump_fixed(name, dict(config=cfg, docs=docs))
+        print(name, ndocs, "docs", [len(d["chunks"]["header"]) for d in docs], "header bytes")
+    for name, (over, ndocs) in LIVE_SNAP_FIXTURES.items():
+        data = _harness("live", dict(LIVE_BASE, **over), 0, ndocs)
+        for d in data["docs"]:
+            d["out"].pop("tree", None)
+        _dump_fixed(name, data)
+        print(name, ndocs, "docs", [len(d["snaps"]) for d in data["docs"]], "summaries")
+
+
+def make_snapshot_fixtures(emit_only=False):
+    make_snapshot_emit_fixtures()
+    if emit_only:
+        return
     for name, (cfg, ndocs) in SNAP_FIXTURES.items():
         with tempfile.TemporaryDirectory() as td:
             cp, op = os.path.join(td, "cfg.json"), os.path.join(td, "out.json")
@@ -403,8 +440,8 @@ def main():
         only = sys.argv[sys.argv.index("--live") + 1].split(",") if len(sys.argv) > sys.argv.index("--live") + 1 else None
         make_live_fixtures(only)
         return
-    if "--snapshots" in sys.argv[1:]:
-        make_snapshot_fixtures()
+    if "--snapshots" in sys.argv[1:]:   # (--snapshots emit: only the emission-only and participant ones)
+        make_snapshot_fixtures(emit_only="emit" in sys.argv[1:])
         return
     if "--farm" in sys.argv[1:]:
         make_farm_fixture()

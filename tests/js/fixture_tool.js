@@ -76,7 +76,8 @@ if (mode === "encode") {
     const { GpuMergeTreeBatch } = require(path.join(repo, "fluidframework_amd", "js", "index.js"));
     const dflt = extra[0] === "default";
     const b = new GpuMergeTreeBatch(fx.docs.length, dflt ? { liveClient: 1 }
-        : { segCapacity: 16384, textCapacity: 1 << 17, liveClient: 1, deltaLogCapacity: 1 << 16 });
+        : { segCapacity: 16384, textCapacity: 1 << 17, liveClient: 1, deltaLogCapacity: 1 << 16,
+            mergeTreeSnapshotChunkSize: fx.config.chunk || 10000 });
     b.loadInitialText(fx.docs.map((d) => d.seed_text));
     const docs = [];
     const deltas = fx.docs.map(() => []);
@@ -95,7 +96,23 @@ if (mode === "encode") {
         const c = cs[i];
         let unseq = [];
         const errs = [];
-        for (const ev of d.events) {
+        // participant summaries the reference wrote (ref_live_snap: [events so far, the local
+        // client's long id, {path: contents}]): batch.snapshots() at the same points must emit
+        // the same blobs (unacked inserts and pending removes elided)
+        let snapsChecked = 0;
+        const checkSnaps = (k) => {
+            for (const [at, , chunks] of d.snaps || []) {
+                if (at !== k) { continue; }
+                const tree = b.snapshots().trees[i];
+                const got = Object.fromEntries(tree.entries.map((e) => [e.path, e.value.contents]));
+                if (JSON.stringify(got) !== JSON.stringify(chunks)) { errs.push(`summary before event ${k}`); }
+                snapsChecked++;
+            }
+        };
+        for (let k = 0; k <= d.events.length; k++) {
+            checkSnaps(k);
+            if (k === d.events.length) { break; }
+            const ev = d.events[k];
             if (ev[0] === "L") {
                 const op = ev[1];
                 let got;
@@ -116,7 +133,7 @@ if (mode === "encode") {
                 unseq = ev[2];
             }
         }
-        docs.push({ doc: d.doc, text: c.getText(), length: c.getLength(), errs });
+        docs.push({ doc: d.doc, text: c.getText(), length: c.getLength(), errs, snaps: snapsChecked });
     });
     b.flush();
     docs.forEach((x, i) => { x.deltas = deltas[i]; });

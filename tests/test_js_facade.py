@@ -288,6 +288,12 @@ def test_js_facade_live_client_matches_reference():
         # mergeTreeDeltaCallback stream: local ops (seq -1, no sequencedMessage), remote ops,
         # propertyDeltas undefined where an outstanding local rewrite blocked a remote annotate
         assert g["deltas"] == d["out"]["deltas"]
+    # batch.snapshots() on the liveClient batch at the points where the reference's participant
+    # wrote its own summary (ref_live_snap): the same blobs, byte for byte
+    fx = gu.load("ref_live_snap")
+    got = _node("live", os.path.join(gu.GOLDEN, "ref_live_snap.json.gz"))
+    for d, g in zip(fx["docs"], got["docs"]):
+        assert g["errs"] == [] and g["snaps"] == len(d["snaps"]) > 0, (d["doc"], g["errs"][:3], g["snaps"])
 
 
 @pytest.mark.gpu

@@ -62,6 +62,26 @@ class MtGenCfg(ctypes.Structure):
                 ("p_insert_props", ctypes.c_uint64), ("p_null", ctypes.c_uint64)]
 
 
+class MtPickQuery(ctypes.Structure):
+    """mt_pick_query (include/mt_replay.h): a launch described for mt_debug_pick."""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "launch", "delta_log", "ordinals", "live", "wpg", "big", "gen_words", "S", "B", "H",
+        "PP", "PH", "UT", "narrow", "packed", "grow")]
+
+
+PICK_LAUNCHES = ("replay_lds", "replay_hbm", "replay_paged", "generate_lds", "generate_hbm",
+                 "generate_paged", "load_convert", "occupancy")   # MT_PICK_* by value
+
+
+def debug_pick(launch, **fields):
+    """(variant name, dynamic LDS bytes) the library picks for the described launch, or None
+    when it has no such kernel; needs no device."""
+    q = MtPickQuery(launch=PICK_LAUNCHES.index(launch), **fields)
+    name, lds = ctypes.create_string_buffer(32), ctypes.c_uint64(0)
+    rc = load().mt_debug_pick(ctypes.byref(q), name, 32, ctypes.byref(lds))
+    return (name.value.decode(), lds.value) if rc == 0 else None
+
+
 # (name, restype, argtypes) for every symbol of include/mt_replay.h
 _P, _I, _U32, _U64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64
 SIGNATURES = [
@@ -118,6 +138,7 @@ SIGNATURES = [
     ("mt_get_delta_log", _I, [_P, _U32, _P, _U32, _P]),
     ("mt_delta_log_reset", _I, [_P]),
     ("mt_debug_raw", _I, [_P, _U32, _P, _U32, _P, _P]),
+    ("mt_debug_pick", _I, [_P, _P, _U32, _P]),
     ("mt_debug_prof", _I, [_P, _P, _I]),
     ("mt_maintenance_counts", _I, [_P, _P]),
     ("mt_checksums", _I, [_P, _P]),

@@ -50,7 +50,8 @@ def needs_build():
 def variants():
     """(name, kernel expression) of every kernel instantiation in csrc/mt_variants.h."""
     text = open(VARIANTS_H).read()
-    return re.findall(r"X\((\w+), \((.*?)\)\)\s*\\?\n", text)
+    return [(name, f"{kernel}<{targs}>")
+            for name, kernel, targs in re.findall(r"X\((\w+), (\w+), \((.*?)\)\)\s*\\?\n", text)]
 
 
 def build(force=False, verbose=False):

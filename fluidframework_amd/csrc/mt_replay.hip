@@ -6,14 +6,17 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mt_replay.h"
 #include "mt_kernels.h"
 #include "mt_variants.h"
 #ifdef MT_SINGLE_TU
-#define MT_VARIANT_DEF(n, k) const void *mtk_##n() { return (const void *)k; }
+#define MT_VARIANT_DEF(n, k, targs) const void *mtk_##n() { return (const void *)(k<MT_UNPAREN targs>); }
 MT_VARIANTS(MT_VARIANT_DEF)
 #endif
 
@@ -1116,6 +1119,27 @@ __global__ void __launch_bounds__(MT_WAVE) k_regen(DevState st, int doc, mt_rege
     }
 }
 
+// Device time of a bulk read-out's kernels: up to two brackets of HIP events, created on first
+// use; `timed` counts the brackets of the last read-out whose kernels have finished
+// (read_timer: mt_last_text_ms, mt_last_props_ms, mt_last_locate).
+struct ReadTimer {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    int timed = 0;
+    hipError_t begin(int k, hipStream_t s) {
+        for (hipEvent_t *e : {&ev[2 * k], &ev[2 * k + 1]})
+            if (!*e) {
+                const hipError_t rc = hipEventCreate(e);
+                if (rc != hipSuccess) return rc;
+            }
+        return hipEventRecord(ev[2 * k], s);
+    }
+    hipError_t end(int k, hipStream_t s) { return hipEventRecord(ev[2 * k + 1], s); }
+    void destroy() {
+        for (hipEvent_t e : ev)
+            if (e) hipEventDestroy(e);
+    }
+};
+
 struct mt_handle {
     int device = 0;
     bool live = false;       // live-client handle (mt_options.live_client)
@@ -1125,13 +1149,10 @@ struct mt_handle {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_load = nullptr, ev_load1 = nullptr;
     bool load_timed = false;   // ev_load / ev_load1 bracket the last snapshot load's kernels
-    hipEvent_t ev_txt[4] = {nullptr, nullptr, nullptr, nullptr};   // mt_get_texts: around its counting pass, around its gather
-    int txt_timed = 0;         // 1: the counting pass was bracketed, 2: the gather as well
-    hipEvent_t ev_prp[4] = {nullptr, nullptr, nullptr, nullptr};   // mt_get_prop_runs_bulk: the same two brackets
-    int prp_timed = 0;
-    hipEvent_t ev_loc[2] = {nullptr, nullptr};   // the bulk segment read-outs' kernel
-    bool loc_timed = false;
-    int64_t loc_n = 0, loc_host = 0;   // queries of the last one, of them answered by the host path
+    // mt_get_texts, mt_get_prop_runs_bulk: around the counting pass, around the gather; the bulk
+    // segment read-outs: around their kernel
+    ReadTimer tm_txt, tm_prp, tm_loc;
+    int64_t loc_n = 0, loc_host = 0;   // queries of the last segment read-out, of them answered by the host path
     // documents per workgroup of the LDS-tier replay (env MT_WPG=2 for two): measured on C2
     // the CU saturates at 16 resident documents (16 -> 18 per CU: 61.8 -> 64.6 ms)
     int wpg = 1;
@@ -1167,6 +1188,14 @@ struct mt_batch {
     uint32_t *props = nullptr;
     int32_t *order = nullptr;     // dispatch order (DevState.order), null when lengths are equal
 };
+// The batch's device arrays at the sizes it holds (mt_batch_free releases them).
+static hipError_t batch_alloc(mt_batch *b) {
+    hipError_t e = hipMalloc(&b->off, ((size_t)b->n_docs + 1) * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMalloc(&b->ops, std::max<uint64_t>(b->n_ops, 1) * sizeof(mt_op_rec));
+    if (e == hipSuccess) e = hipMalloc(&b->text, std::max<uint64_t>(b->text_len, 1) * sizeof(uint16_t));
+    if (e == hipSuccess) e = hipMalloc(&b->props, std::max<uint64_t>(b->props_len, 1) * sizeof(uint32_t));
+    return e;
+}
 // Longest-first dispatch order of a batch whose documents differ in length (stable: equal
 // lengths keep index order); none when every document has the same number of messages.
 static bool set_order(mt_batch *b, const int64_t *off) {
@@ -1191,39 +1220,152 @@ static bool set_order(mt_batch *b, const int64_t *off) {
         }                                                                          \
     } while (0)
 
-// Launches through the kernel pointers of mt_variants.h (hipLaunchKernel with the kernels'
-// exact parameter types; errors are read with hipGetLastError as for hipLaunchKernelGGL)
-static void launch_replay(const void *k, dim3 g, dim3 b, size_t lds, hipStream_t s, DevState st, const mt_op_rec *ops,
-                          const int64_t *off, const uint16_t *tin, const uint32_t *pin, TierCaps caps) {
-    void *a[] = {&st, &ops, &off, &tin, &pin, &caps};
-    (void)hipLaunchKernel(k, g, b, a, lds, s);
+// Device memory that a function allocates and frees itself (n elements of T; bytes by
+// default): freed on every return, HIPCHK's included.  release() hands it to another owner.
+template <class T = uint8_t> struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() {
+        if (p) hipFree(p);
+    }
+    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)); }
+    T *release() {
+        T *q = p;
+        p = nullptr;
+        return q;
+    }
+};
+
+// ---------------------------------------------------------------- kernel variants
+// One row per entry of MT_VARIANTS: the kernel and the facts that select it and size its
+// dynamic LDS, read off the tier type that instantiates it -- a row cannot disagree with its
+// kernel.  Every launch of a replay / generate / load-convert kernel asks pick_flat or
+// pick_paged for its row and its LDS bytes and goes through launch_variant.
+enum KFamily { K_REPLAY, K_REPLAY_PAGED, K_GENERATE, K_GENERATE_PAGED, K_LOAD_CONVERT };
+#define MT_FAM_k_replay K_REPLAY
+#define MT_FAM_k_replay_paged K_REPLAY_PAGED
+#define MT_FAM_k_generate K_GENERATE
+#define MT_FAM_k_generate_paged K_GENERATE_PAGED
+#define MT_FAM_k_load_convert K_LOAD_CONVERT
+struct Variant {
+    const char *name;
+    const void *(*kernel)();
+    KFamily fam;
+    bool log;                 // T::kLog
+    bool lds, live;           // flat tiers: T::kLds, T::kLive
+    int wpg;                  // k_replay: documents per workgroup
+    int ob;                   // paged tiers: sizeof(T::O_v), 4 for a narrow tier
+    bool big, packed, hm;     // T::kBig, T::kPacked, T::kHM
+    int PP, PH, UT;           // T::kPP / kPH / kUT (0: the launch's)
+};
+template <class T, int WPG = 1>
+static constexpr Variant variant_row(const char *name, const void *(*kernel)(), KFamily fam) {
+    if constexpr (T::kPaged)
+        return Variant{name, kernel, fam, T::kLog, true, false, 1, (int)sizeof(typename T::O_v),
+                       T::kBig, T::kPacked, T::kHM, T::kPP, T::kPH, T::kUT};
+    else
+        return Variant{name, kernel, fam, T::kLog, T::kLds, T::kLive, WPG, 0, false, false, false, 0, 0, 0};
 }
-static void launch_replay_paged(const void *k, dim3 g, dim3 b, size_t lds, hipStream_t s, DevState st,
-                                const mt_op_rec *ops, const int64_t *off, const uint16_t *tin, const uint32_t *pin,
-                                int use_resume, PagedCaps pc, PagedSlice sl) {
-    void *a[] = {&st, &ops, &off, &tin, &pin, &use_resume, &pc, &sl};
-    (void)hipLaunchKernel(k, g, b, a, lds, s);
+#define MT_VARIANT_ROW(n, k, targs) variant_row<MT_UNPAREN targs>(#n, mtk_##n, MT_FAM_##k),
+static const Variant kVariants[] = {MT_VARIANTS(MT_VARIANT_ROW)};
+
+struct HandleFacts {
+    bool log, ordinals, live;   // st.DL > 0, mt_options.segment_ordinals, mt_options.live_client
+    int wpg;                    // documents per workgroup asked of the LDS-tier replay
+};
+static HandleFacts facts(const mt_handle *h) { return HandleFacts{h->st.DL > 0, h->ordinals, h->live, h->wpg}; }
+struct Pick {
+    const Variant *v;   // nullptr: the library has no such kernel (an error, never a fall-back)
+    size_t lds;         // its dynamic LDS bytes
+};
+
+// The flat family (k_replay, k_generate).  caps.S > 0: the LDS tier's launch, else the HBM
+// tier's.  The generator keeps neither a delta log nor live state; two documents per
+// workgroup exist for the plain observer replay only (any other handle runs one).
+// LDS: WPG slices of the kernel's own lds_layout(T::kLds, S, B, H, gen_words).
+static Pick pick_flat(KFamily fam, const HandleFacts &f, const TierCaps &c, int gen_words) {
+    const bool lds = c.S > 0, gen = fam == K_GENERATE;
+    const bool live = !gen && f.live, log = !gen && f.log;
+    const Variant *v = nullptr;
+    for (const int wpg : {lds && !gen ? f.wpg : 1, 1})
+        for (const Variant &r : kVariants)
+            if (!v && r.fam == fam && r.lds == lds && r.live == live && r.log == log && r.wpg == wpg) v = &r;
+    return Pick{v, v ? v->wpg * (size_t)lds_layout(v->lds, c.S, c.B, c.H, gen_words).total : 0};
 }
-static void launch_generate(const void *k, dim3 g, dim3 b, size_t lds, hipStream_t s, DevState st, mt_gen_cfg cfg,
-                            uint32_t doc_base, mt_op_rec *ops_out, uint16_t *text_out, uint32_t *props_out,
-                            int64_t tstride, int64_t pstride, int32_t *fail_out, int32_t *dbg_len, int64_t *used_out,
-                            TierCaps caps) {
-    void *a[] = {&st, &cfg, &doc_base, &ops_out, &text_out, &props_out, &tstride, &pstride, &fail_out, &dbg_len,
-                 &used_out, &caps};
-    (void)hipLaunchKernel(k, g, b, a, lds, s);
+
+// Documents of many pages replay with their page metadata in HBM (TierPagedT kHM: no LDS per
+// page instead of 12 bytes, so more of them share a CU); the bench's C3 / C4 documents (< 300
+// pages) keep it in LDS (no global load on their page searches).  Delta-logging handles take
+// the kHM tier too (P_HM_LOG, P_BIG_HM_LOG); segment-ordinal handles keep the LDS metadata.
+#ifndef MT_HM_PAGES
+#define MT_HM_PAGES 512
+#endif
+// The kernel's own paged_layout call: k_replay_paged substitutes its compile-time capacities
+// (eff_caps) and passes kPacked / kHM; k_generate_paged adds the generator's words;
+// k_load_convert neither.
+static size_t paged_lds_bytes(const Variant &v, PagedCaps pc, int gen_words) {
+    if (v.fam != K_REPLAY_PAGED) return paged_layout(pc.PP, pc.PH, pc.UT, gen_words, v.ob).total;
+    if (v.PP > 0) pc.PP = v.PP;
+    if (v.PH > 0) pc.PH = v.PH;
+    if (v.UT > 0) pc.UT = v.UT;
+    return paged_layout(pc.PP, pc.PH, pc.UT, 0, v.ob, v.packed, v.hm).total;
 }
-static void launch_generate_paged(const void *k, dim3 g, dim3 b, size_t lds, hipStream_t s, DevState st,
-                                  mt_gen_cfg cfg, uint32_t doc_base, mt_op_rec *ops_out, uint16_t *text_out,
-                                  uint32_t *props_out, int64_t tstride, int64_t pstride, int32_t *fail_out,
-                                  int32_t *dbg_len, int64_t *used_out, PagedCaps pc) {
-    void *a[] = {&st, &cfg, &doc_base, &ops_out, &text_out, &props_out, &tstride, &pstride, &fail_out, &dbg_len,
-                 &used_out, &pc};
-    (void)hipLaunchKernel(k, g, b, a, lds, s);
+// The paged family (k_replay_paged, k_generate_paged, k_load_convert); big: the launch serves
+// the big region's documents (the growth step's).  A kernel whose compile-time capacities are
+// the launch's wins over the run-time one (the bench's C3 and C4 tight tiers, DESIGN section
+// 11).  The generator keeps no delta log; load-convert compiles it in for the canonical
+// ordinals only.  sizing: mt_create's occupancy query, which sizes the sliced schedule by the
+// tier's plain run-time kernel whatever the launches later run.
+static Pick pick_paged(KFamily fam, const HandleFacts &f, const PagedCaps &pc, bool big, int gen_words,
+                       bool sizing = false) {
+    const bool log = fam == K_REPLAY_PAGED ? f.log : (fam == K_LOAD_CONVERT ? f.ordinals : false);
+    const bool hm = fam == K_REPLAY_PAGED && !sizing && !pc.packed && !pc.narrow && !f.ordinals &&
+                    pc.PP >= MT_HM_PAGES;
+    const Variant *v = nullptr;
+    for (const bool fixed : {true, false})
+        for (const Variant &r : kVariants) {
+            if (v || r.fam != fam || r.log != log || (r.ob == 4) != (pc.narrow != 0) || r.big != big ||
+                r.packed != (pc.packed != 0) || r.hm != hm || (r.PP > 0) != fixed)
+                continue;
+            if (!fixed || (!sizing && r.PP == pc.PP && r.PH == pc.PH && r.UT == pc.UT)) v = &r;
+        }
+    return Pick{v, v ? paged_lds_bytes(*v, pc, gen_words) : 0};
 }
-static void launch_load_convert(const void *k, dim3 g, dim3 b, size_t lds, hipStream_t s, DevState st, LoadScratch sc,
-                                PagedCaps pc, int lo) {
-    void *a[] = {&st, &sc, &pc, &lo};
-    (void)hipLaunchKernel(k, g, b, a, lds, s);
+
+// A launch that needs more than the 64 KiB every kernel may use raises the kernel's
+// MaxDynamicSharedMemorySize first.  The attribute belongs to the process (per device), not to
+// a handle: the largest value set so far is kept per kernel and never lowered, so a handle with
+// a smaller layout cannot take the limit away from under another one.
+static hipError_t raise_lds_limit(const void *kernel, size_t lds) {
+    if (lds <= 64 * 1024) return hipSuccess;
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, size_t> set;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t &cur = set[{dev, kernel}];
+    if (lds <= cur) return hipSuccess;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) cur = lds;
+    return e;
+}
+// One wave per document, p.v->wpg documents per workgroup; args: the kernel's exact parameters
+// (errors are read with hipGetLastError as for hipLaunchKernelGGL).
+static hipError_t launch_variant(const Pick &p, uint32_t n_docs, hipStream_t s, void **args) {
+    if (!p.v) return hipErrorInvalidDeviceFunction;
+    const void *k = p.v->kernel();
+    const hipError_t e = raise_lds_limit(k, p.lds);
+    if (e != hipSuccess) return e;
+    const uint32_t w = (uint32_t)p.v->wpg;
+    (void)hipLaunchKernel(k, dim3((n_docs + w - 1) / w), dim3(MT_WAVE * w), args, p.lds, s);
+    return hipGetLastError();
+}
+static hipError_t launch_replay(const Pick &p, mt_handle *h, const mt_batch *b, TierCaps caps) {
+    void *a[] = {&h->st, (void *)&b->ops, (void *)&b->off, (void *)&b->text, (void *)&b->props, &caps};
+    return launch_variant(p, h->n_docs, h->stream, a);
 }
 
 static int mt_settle(mt_handle *h);
@@ -1289,9 +1431,106 @@ static std::string validate_batch(uint32_t n_docs, const int64_t *off, const mt_
     max_cli = mc;
     return std::string();
 }
-static size_t tier_lds_bytes(bool seg_in_lds, const TierCaps &c, int gen_words) {
-    return lds_layout(seg_in_lds, c.S, c.B, c.H, gen_words).total;
+
+// ---------------------------------------------------------------- bulk read-out harness
+// What mt_get_texts, mt_get_prop_runs_bulk and the bulk segment read-outs (locate) share; each
+// keeps its kernels, its error text and, for locate, its host path.
+
+// The queries of a bulk read-out: fewer than 2^31, each naming a document of the handle
+// (docs == nullptr: query q reads document q).
+static int check_queries(mt_handle *h, const char *name, uint32_t n, const uint32_t *docs) {
+    if (n > 0x7FFFFFFFu || (!docs && n > h->n_docs)) return MT_E_INVALID;
+    for (uint32_t q = 0; docs && q < n; q++)
+        if (docs[q] >= h->n_docs) {
+            h->err = std::string(name) + ": query " + std::to_string(q) + ": no document " + std::to_string(docs[q]);
+            return MT_E_INVALID;
+        }
+    return 0;
 }
+// The query columns on the device, one allocation: `extra` bytes of the read-out's own (a
+// multiple of 8, 16-byte aligned), then up to four columns of n words; an absent column's
+// pointer is null, as the kernels expect.
+struct QueryCols {
+    DevBuf<> buf;
+    uint8_t *extra = nullptr;
+    void *col[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipError_t upload(uint32_t n, std::initializer_list<const void *> cols, size_t extra_bytes) {
+        hipError_t e = buf.alloc(extra_bytes + cols.size() * (size_t)n * 4);
+        extra = buf.p;
+        int i = 0;
+        for (const void *c : cols) {
+            void *d = buf.p + extra_bytes + (size_t)i * n * 4;
+            if (c && e == hipSuccess) e = hipMemcpy(d, c, (size_t)n * 4, hipMemcpyHostToDevice);
+            col[i++] = c ? d : nullptr;
+        }
+        return e;
+    }
+};
+static int read_timer(mt_handle *h, const ReadTimer &t, float *out /* [2] */) {
+    out[0] = out[1] = 0.f;
+    if (t.timed >= 1) HIPCHK(h, hipEventElapsedTime(&out[0], t.ev[0], t.ev[1]));
+    if (t.timed >= 2) HIPCHK(h, hipEventElapsedTime(&out[1], t.ev[2], t.ev[3]));
+    return 0;
+}
+// No query: every offset array is its single 0.
+static int empty_offsets(mt_handle *h, std::initializer_list<int64_t *> off, bool device) {
+    for (int64_t *o : off)
+        if (device)
+            HIPCHK(h, hipMemset(o, 0, 8));
+        else
+            o[0] = 0;
+    return 0;
+}
+// k streams of per-query counts (device, n each) -> their exclusive prefix sums off[i][n + 1]
+// and totals: on the host for host results (as mt_extract_snapshots takes them), by k_text_scan
+// for device results (off[i]: device arrays).  Returns with the stream idle.
+static int scan_counts(mt_handle *h, uint32_t n, int k, int64_t *const *d_cnt, int64_t *const *off, bool device,
+                       int64_t *total) {
+    if (device) {
+        for (int i = 0; i < k; i++) {
+            hipLaunchKernelGGL(k_text_scan, dim3(1), dim3(1024), 0, h->stream, d_cnt[i], (int)n, off[i]);
+            HIPCHK(h, hipGetLastError());
+        }
+        for (int i = 0; i < k; i++)
+            HIPCHK(h, hipMemcpyAsync(&total[i], off[i] + n, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return 0;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < k; i++) {
+        HIPCHK(h, hipMemcpy(off[i] + 1, d_cnt[i], (size_t)n * 8, hipMemcpyDeviceToHost));
+        off[i][0] = 0;
+        for (uint32_t q = 0; q < n; q++) off[i][q + 1] += off[i][q];
+        total[i] = off[i][n];
+    }
+    return 0;
+}
+// With the totals known: RO_DONE without an output to fill (sizing only) or without results,
+// MT_E_OVERFLOW (message from overflow_msg) when the outputs are too small -- they stay
+// untouched, the offsets are already written -- else RO_GATHER.
+enum { RO_DONE = 0, RO_GATHER = 1 };
+template <class Msg> static int after_counts(mt_handle *h, bool sizing, bool fits, bool empty, Msg overflow_msg) {
+    if (sizing) return RO_DONE;
+    if (!fits) {
+        h->err = overflow_msg();
+        return MT_E_OVERFLOW;
+    }
+    return empty ? RO_DONE : RO_GATHER;
+}
+// Where a gather writes: the caller's device array, or (host results) device memory of this
+// call that copy_out then copies to the caller's host array.
+template <class T> struct OutStage {
+    DevBuf<T> own;
+    T *p = nullptr;
+    hipError_t open(void *caller_dev, bool device, size_t count) {
+        const hipError_t e = device ? hipSuccess : own.alloc(count);
+        p = device ? (T *)caller_dev : own.p;
+        return e;
+    }
+    hipError_t copy_out(void *host, size_t count) const {
+        return own.p && count ? hipMemcpy(host, own.p, count * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess;
+    }
+};
 
 extern "C" {
 
@@ -1350,7 +1589,7 @@ mt_handle *mt_create(uint32_t n_docs, const mt_options *opt) {
         // heap stays far below S_l (C2 needs < 96 at S_l 192: 0 hand-overs); a smaller heap
         // is a smaller LDS footprint = more documents per CU (profiles/r1 sweep: 74.9 -> 68.9 ms)
         h->lds.H = std::min(st.H, std::max(64, S_l / 2));
-        if (tier_lds_bytes(true, h->lds, 0) > 60 * 1024) h->lds = TierCaps{0, 0, 0, 0};
+        if (lds_layout(true, h->lds.S, h->lds.B, h->lds.H, 0).total > 60 * 1024) h->lds = TierCaps{0, 0, 0, 0};
     }
     if (o.page_capacity > 0) {
         st.PP = std::min(o.page_capacity, 65535);
@@ -1374,34 +1613,21 @@ mt_handle *mt_create(uint32_t n_docs, const mt_options *opt) {
             delete h;
             return nullptr;
         }
-        if (lb > 64 * 1024) {
-            const void *ks[] = {MTK(P_LOG), MTK(P_FULL), MTK(P_HM), MTK(P_HM_LOG),
-                                MTK(GP_FULL),
-                                MTK(P_NARROW_LOG),
-                                MTK(P_NARROW),
-                                MTK(GP_NARROW),
-                                MTK(LC_FAST),
-                                MTK(LC_LOG),
-                                MTK(P_PACKED_LOG),
-                                MTK(P_PACKED)};
-            for (const void *k : ks)
-                if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb) != hipSuccess) {
-                    delete h;
-                    return nullptr;
-                }
+        // a device whose kernels cannot have that much fails the creation, not the first launch
+        // (asked of the last tier's kernel; every launch raises its own kernel's limit itself)
+        if (raise_lds_limit(pick_paged(K_REPLAY_PAGED, facts(h), h->pg_full, false, 0, true).v->kernel(), lb) !=
+            hipSuccess) {
+            delete h;
+            return nullptr;
         }
         // documents resident at once in the first paged launch (the sliced schedule's round)
         h->paged_slices = std::min(std::max(o.paged_slices, 0), 256);
         if (h->paged_slices > 1) {
             const PagedCaps &c = h->pg_tight.PP ? h->pg_tight : h->pg_full;
-            const size_t lt = paged_layout(c.PP, c.PH, c.UT, 0, c.narrow ? 4 : 8).total;
-            const void *k = st.DL ? (c.narrow ? MTK(P_NARROW_LOG)
-                                              : MTK(P_LOG))
-                                  : (c.narrow ? MTK(P_NARROW)
-                                              : MTK(P_FULL));
+            const Pick p = pick_paged(K_REPLAY_PAGED, facts(h), c, false, 0, true);
             int per_cu = 0, cus = 0;
             hipDeviceProp_t prop;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, MT_WAVE, lt) == hipSuccess &&
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, p.v->kernel(), MT_WAVE, p.lds) == hipSuccess &&
                 hipGetDeviceProperties(&prop, h->device) == hipSuccess)
                 cus = prop.multiProcessorCount;
             h->pg_resident = per_cu * cus;
@@ -1502,12 +1728,7 @@ void mt_destroy(mt_handle *h) {
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->ev_load) hipEventDestroy(h->ev_load);
     if (h->ev_load1) hipEventDestroy(h->ev_load1);
-    for (hipEvent_t e : h->ev_txt)
-        if (e) hipEventDestroy(e);
-    for (hipEvent_t e : h->ev_prp)
-        if (e) hipEventDestroy(e);
-    for (hipEvent_t e : h->ev_loc)
-        if (e) hipEventDestroy(e);
+    for (ReadTimer *t : {&h->tm_txt, &h->tm_prp, &h->tm_loc}) t->destroy();
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
 }
@@ -1532,21 +1753,14 @@ int mt_start_collaboration(mt_handle *h, const int32_t *min_seq, const int32_t *
             return MT_E_INVALID;
         }
     SETTLE(h);
-    int32_t *d_w = nullptr;
-    HIPCHK(h, hipMalloc(&d_w, (size_t)h->n_docs * 8 + 8));
-    bool ok = hipMemcpyAsync(d_w, min_seq, (size_t)h->n_docs * 4, hipMemcpyHostToDevice, h->stream) == hipSuccess &&
-              hipMemcpyAsync(d_w + h->n_docs, cur_seq, (size_t)h->n_docs * 4, hipMemcpyHostToDevice, h->stream) ==
-                  hipSuccess;
-    if (ok) {
-        hipLaunchKernelGGL(k_set_window, dim3((h->n_docs + 255) / 256), dim3(256), 0, h->stream, h->st, d_w,
-                           d_w + h->n_docs);
-        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
-    }
-    hipFree(d_w);
-    if (!ok) {
-        h->err = "mt_start_collaboration failed";
-        return MT_E_HIP;
-    }
+    DevBuf<int32_t> d_w;   // [min_seq | cur_seq]
+    HIPCHK(h, d_w.alloc((size_t)h->n_docs * 2 + 2));
+    HIPCHK(h, hipMemcpyAsync(d_w.p, min_seq, (size_t)h->n_docs * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_w.p + h->n_docs, cur_seq, (size_t)h->n_docs * 4, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_set_window, dim3((h->n_docs + 255) / 256), dim3(256), 0, h->stream, h->st, d_w.p,
+                       d_w.p + h->n_docs);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
 
@@ -1624,10 +1838,7 @@ mt_batch *mt_batch_upload(mt_handle *h, const int64_t *doc_op_off, const mt_op_r
     b->n_ops = n_ops;
     b->text_len = text_len;
     b->props_len = props_len;
-    bool ok = hipMalloc(&b->off, (h->n_docs + 1) * sizeof(int64_t)) == hipSuccess &&
-              hipMalloc(&b->ops, std::max<uint64_t>(n_ops, 1) * sizeof(mt_op_rec)) == hipSuccess &&
-              hipMalloc(&b->text, std::max<uint64_t>(text_len, 1) * sizeof(uint16_t)) == hipSuccess &&
-              hipMalloc(&b->props, std::max<uint64_t>(props_len, 1) * sizeof(uint32_t)) == hipSuccess;
+    bool ok = batch_alloc(b) == hipSuccess;
     if (ok) {
         ok = hipMemcpy(b->off, doc_op_off, (h->n_docs + 1) * sizeof(int64_t), hipMemcpyHostToDevice) == hipSuccess;
         if (ok && n_ops) ok = hipMemcpy(b->ops, ops, n_ops * sizeof(mt_op_rec), hipMemcpyHostToDevice) == hipSuccess;
@@ -1654,66 +1865,10 @@ __global__ void k_mark_big(DevState st, const int64_t *off, int resume_set) {
 }
 // One paged launch over every document (those not at stage pc.stage exit at once); big: the
 // documents of the big region (the growth step's launches).
-// Documents of many pages replay with their page metadata in HBM (TierPagedT kHM: no LDS per
-// page instead of 12 bytes, so more of them share a CU); the bench's C3 / C4 documents (< 300
-// pages) keep it in LDS (no global load on their page searches).  Delta-logging handles take
-// the kHM tier too (P_HM_LOG, P_BIG_HM_LOG); segment-ordinal handles keep the LDS metadata.
-#ifndef MT_HM_PAGES
-#define MT_HM_PAGES 512
-#endif
-static bool use_hm(const mt_handle *h, const PagedCaps &pc) {
-    return !pc.packed && !pc.narrow && !h->ordinals && pc.PP >= MT_HM_PAGES;
-}
-static int launch_paged(mt_handle *h, const mt_batch *b, const PagedCaps &pc, int res, const PagedSlice &sl,
-                        bool big = false) {
-    const bool hm = use_hm(h, pc);
-    const size_t lb = paged_layout(pc.PP, pc.PH, pc.UT, 0, pc.narrow ? 4 : 8, pc.packed != 0, hm).total;
-    const dim3 g(h->n_docs), blk(MT_WAVE);
-    // the bench's C3 tight tier with its capacities fixed at compile time (same code, constant
-    // LDS layout: bench.capacities)
-    if (!big && !pc.packed && pc.narrow && !h->st.DL && pc.PP == 192 && pc.PH == 192 && pc.UT == 220)
-        launch_replay_paged(MTK(P_C3), g, blk, lb, h->stream,
-                           h->st, b->ops, b->off, b->text, b->props, res, pc, sl);
-    else if (!big && pc.packed && !h->st.DL && pc.PP == 224 && pc.PH == 900 && pc.UT == 1900)   // the bench's C4 tier
-        launch_replay_paged(MTK(P_C4), g, blk, lb, h->stream,
-                           h->st, b->ops, b->off, b->text, b->props, res, pc, sl);
-    else if (pc.packed && h->st.DL)
-        launch_replay_paged(MTK(P_PACKED_LOG), g, blk, lb, h->stream, h->st, b->ops,
-                           b->off, b->text, b->props, res, pc, sl);
-    else if (pc.packed)
-        launch_replay_paged(MTK(P_PACKED), g, blk, lb, h->stream, h->st,
-                           b->ops, b->off, b->text, b->props, res, pc, sl);
-    else if (big && h->st.DL && hm)
-        launch_replay_paged(MTK(P_BIG_HM_LOG), g, blk, lb, h->stream, h->st, b->ops,
-                           b->off, b->text, b->props, res, pc, sl);
-    else if (big && h->st.DL)
-        launch_replay_paged(MTK(P_BIG_LOG), g, blk, lb, h->stream, h->st, b->ops,
-                           b->off, b->text, b->props, res, pc, sl);
-    else if (big && hm)
-        launch_replay_paged(MTK(P_BIG_HM), g, blk, lb, h->stream, h->st, b->ops,
-                           b->off, b->text, b->props, res, pc, sl);
-    else if (big)
-        launch_replay_paged(MTK(P_BIG), g, blk, lb, h->stream, h->st, b->ops,
-                           b->off, b->text, b->props, res, pc, sl);
-    else if (h->st.DL && hm)
-        launch_replay_paged(MTK(P_HM_LOG), g, blk, lb, h->stream, h->st, b->ops, b->off, b->text,
-                           b->props, res, pc, sl);
-    else if (h->st.DL && pc.narrow)
-        launch_replay_paged(MTK(P_NARROW_LOG), g, blk, lb, h->stream, h->st, b->ops, b->off,
-                           b->text, b->props, res, pc, sl);
-    else if (h->st.DL)
-        launch_replay_paged(MTK(P_LOG), g, blk, lb, h->stream, h->st, b->ops, b->off, b->text,
-                           b->props, res, pc, sl);
-    else if (pc.narrow)
-        launch_replay_paged(MTK(P_NARROW), g, blk, lb, h->stream, h->st, b->ops, b->off,
-                           b->text, b->props, res, pc, sl);
-    else if (hm)
-        launch_replay_paged(MTK(P_HM), g, blk, lb, h->stream, h->st, b->ops, b->off, b->text,
-                           b->props, res, pc, sl);
-    else
-        launch_replay_paged(MTK(P_FULL), g, blk, lb, h->stream, h->st, b->ops, b->off, b->text,
-                           b->props, res, pc, sl);
-    HIPCHK(h, hipGetLastError());
+static int launch_paged(mt_handle *h, const mt_batch *b, PagedCaps pc, int res, PagedSlice sl, bool big = false) {
+    const Pick p = pick_paged(K_REPLAY_PAGED, facts(h), pc, big, 0);
+    void *a[] = {&h->st, (void *)&b->ops, (void *)&b->off, (void *)&b->text, (void *)&b->props, &res, &pc, &sl};
+    HIPCHK(h, launch_variant(p, h->n_docs, h->stream, a));
     return 0;
 }
 
@@ -1730,25 +1885,7 @@ int mt_batch_apply_async(mt_handle *h, const mt_batch *b) {
     if (h->lds.S > 0) {
         // LDS tier for every document; the ones that outgrow it are flagged and replayed
         // from HBM by the second launch (whose other workgroups exit at once)
-        if (h->live && h->st.DL)
-            launch_replay(MTK(R_LIVELDS_LOG), dim3(h->n_docs), dim3(MT_WAVE),
-                               tier_lds_bytes(true, h->lds, 0), h->stream, h->st, b->ops, b->off, b->text, b->props,
-                               h->lds);
-        else if (h->live)
-            launch_replay(MTK(R_LIVELDS), dim3(h->n_docs), dim3(MT_WAVE),
-                               tier_lds_bytes(true, h->lds, 0), h->stream, h->st, b->ops, b->off, b->text, b->props,
-                               h->lds);
-        else if (h->st.DL)
-            launch_replay(MTK(R_LDS_LOG), dim3(h->n_docs), dim3(MT_WAVE), tier_lds_bytes(true, h->lds, 0),
-                               h->stream, h->st, b->ops, b->off, b->text, b->props, h->lds);
-        else if (h->wpg == 2)
-            launch_replay(MTK(R_LDS2), dim3((h->n_docs + 1) / 2), dim3(2 * MT_WAVE),
-                               2 * tier_lds_bytes(true, h->lds, 0), h->stream, h->st, b->ops, b->off, b->text, b->props,
-                               h->lds);
-        else
-            launch_replay(MTK(R_LDS), dim3(h->n_docs), dim3(MT_WAVE), tier_lds_bytes(true, h->lds, 0),
-                               h->stream, h->st, b->ops, b->off, b->text, b->props, h->lds);
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch_replay(pick_flat(K_REPLAY, facts(h), h->lds, 0), h, b, h->lds));
     } else {
         HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->st.retry, 1, h->n_docs, h->stream));
     }
@@ -1800,19 +1937,10 @@ int mt_batch_apply_async(mt_handle *h, const mt_batch *b) {
                 if (rc) return rc;
             }
         }
-    } else if (h->live && h->st.DL)
-        launch_replay(MTK(R_LIVE_LOG), dim3(h->n_docs), dim3(MT_WAVE), tier_lds_bytes(false, live_caps(h), 0),
-                           h->stream, h->st, b->ops, b->off, b->text, b->props, live_caps(h));
-    else if (h->live)
-        launch_replay(MTK(R_LIVE), dim3(h->n_docs), dim3(MT_WAVE), tier_lds_bytes(false, live_caps(h), 0),
-                           h->stream, h->st, b->ops, b->off, b->text, b->props, live_caps(h));
-    else if (h->st.DL)
-        launch_replay(MTK(R_GLB_LOG), dim3(h->n_docs), dim3(MT_WAVE), tier_lds_bytes(false, glb_caps(h), 0),
-                           h->stream, h->st, b->ops, b->off, b->text, b->props, glb_caps(h));
-    else
-        launch_replay(MTK(R_GLB), dim3(h->n_docs), dim3(MT_WAVE), tier_lds_bytes(false, glb_caps(h), 0),
-                           h->stream, h->st, b->ops, b->off, b->text, b->props, glb_caps(h));
-    HIPCHK(h, hipGetLastError());
+    } else {   // the HBM tier: a live handle's hands documents that could outgrow it to the live growth step
+        const TierCaps caps = h->live ? live_caps(h) : glb_caps(h);
+        HIPCHK(h, launch_replay(pick_flat(K_REPLAY, facts(h), caps, 0), h, b, caps));
+    }
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     h->timed = true;
     if (h->st.PP > 0 || h->live) {   // its last paged / live tier may hand documents to a growth step
@@ -1954,35 +2082,29 @@ static int regrow(mt_handle *h, const std::vector<uint32_t> &moving, const Paged
             items.push_back(MigItem{(int32_t)d, h->bslot_h[d], slots});
             slots++;
         }
-    PagedRegion R;
-    if (!alloc_region(R, std::max(slots, 1), c, h->ordinals, T, P, UM, OA)) {
+    struct NewRegion {   // freed unless it is installed as st.big
+        PagedRegion R{};
+        ~NewRegion() { free_region(R); }
+    } nr;
+    if (!alloc_region(nr.R, std::max(slots, 1), c, h->ordinals, T, P, UM, OA)) {
         (void)hipGetLastError();
         h->err = "growth step: device allocation of the big region failed";
         return MT_E_NOMEM;
     }
-    MigItem *d_items = nullptr;
-    if (hipMalloc(&d_items, items.size() * sizeof(MigItem)) != hipSuccess) {
-        free_region(R);
-        return MT_E_NOMEM;
-    }
-    HIPCHK(h, hipMemcpy(d_items, items.data(), items.size() * sizeof(MigItem), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_migrate_paged, dim3((uint32_t)items.size()), dim3(MT_WAVE), 0, h->stream, st, st.big, R,
-                       (const MigItem *)d_items);
+    DevBuf<MigItem> d_items;
+    if (d_items.alloc(items.size()) != hipSuccess) return MT_E_NOMEM;
+    HIPCHK(h, hipMemcpy(d_items.p, items.data(), items.size() * sizeof(MigItem), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_migrate_paged, dim3((uint32_t)items.size()), dim3(MT_WAVE), 0, h->stream, st, st.big, nr.R,
+                       (const MigItem *)d_items.p);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    hipFree(d_items);
     HIPCHK(h, hipMemcpy(st.bslot, nb.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
     free_region(st.big);
-    st.big = R;
+    st.big = nr.R;
+    nr.R = PagedRegion{};
     h->bslot_h = nb;
     h->n_big = (uint32_t)slots;
     h->big_caps = PagedCaps{c.PP, c.PH, c.UT, 0, 3, 0, 1};
-    const size_t lb = paged_layout(c.PP, c.PH, c.UT, 0, 8).total;
-    if (lb > 64 * 1024) {
-        const void *ks[] = {MTK(P_BIG_LOG), MTK(P_BIG_HM_LOG),
-                            MTK(P_BIG), MTK(P_BIG_HM)};
-        for (const void *k : ks) HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
-    }
     return 0;
 }
 
@@ -2285,13 +2407,7 @@ static int live_grow_loop(mt_handle *h, const mt_batch *b) {
         TierCaps caps = glb_caps(h);
         caps.resume = 1;
         caps.grow = 1;
-        if (st.DL)
-            launch_replay(MTK(R_LIVE_LOG), dim3(h->n_docs), dim3(MT_WAVE), tier_lds_bytes(false, caps, 0), h->stream,
-                          st, b->ops, b->off, b->text, b->props, caps);
-        else
-            launch_replay(MTK(R_LIVE), dim3(h->n_docs), dim3(MT_WAVE), tier_lds_bytes(false, caps, 0), h->stream, st,
-                          b->ops, b->off, b->text, b->props, caps);
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch_replay(pick_flat(K_REPLAY, facts(h), caps, 0), h, b, caps));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     h->err = "live growth step: no progress after 40 rounds";
@@ -2636,6 +2752,14 @@ mt_snapshots *mt_snapshots_upload(mt_handle *h, const int64_t *doc_seg_off, cons
                                      props_len, min_seq, cur_seq);
 }
 
+// the staged headers of set s become paged documents at capacities pc (big: in the big region);
+// a segment-ordinal handle's kernel derives the canonical ordinals (reloadFromSegments)
+static hipError_t launch_load_convert(mt_handle *h, const mt_snapshots *s, PagedCaps pc, bool big) {
+    LoadScratch sc = s->sc;
+    int lo = (int)s->doc_lo;
+    void *a[] = {&h->st, &sc, &pc, &lo};
+    return launch_variant(pick_paged(K_LOAD_CONVERT, facts(h), pc, big, 0), s->n_docs, h->stream, a);
+}
 // A staged header that does not fit the paged capacities it was converted at (pages, the
 // unsettled table: k_load_convert left it with MT_DOC_CAPACITY and the cause) is handed to the
 // growth step's big region, as a replayed document that outgrows them is (grow_loop): what ran
@@ -2675,12 +2799,7 @@ static int load_grow(mt_handle *h, const mt_snapshots *s) {
             xh.pad[HDR_DIAG] = 0;
             HIPCHK(h, hipMemcpy(st.hdr + d, &xh, sizeof(DocHdr), hipMemcpyHostToDevice));
         }
-        const PagedCaps pc = h->big_caps;
-        const size_t lb = paged_layout(pc.PP, pc.PH, pc.UT, 0, 8).total;
-        const void *k = h->ordinals ? MTK(LC_BIG_LOG) : MTK(LC_BIG_FAST);
-        if (lb > 64 * 1024) HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
-        launch_load_convert(k, dim3(N), dim3(MT_WAVE), lb, h->stream, h->st, s->sc, pc, (int)s->doc_lo);
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch_load_convert(h, s, h->big_caps, true));
         cur = nc;
     }
     return 0;
@@ -2704,15 +2823,7 @@ int mt_snapshots_load_async(mt_handle *h, const mt_snapshots *s) {
                        s->text, s->props, s->min_seq, s->cur_seq, s->sc, (int)s->doc_lo);
     HIPCHK(h, hipGetLastError());
     if (s->any_big) {
-        const PagedCaps &pc = h->pg_full;
-        const size_t lb = paged_layout(pc.PP, pc.PH, pc.UT, 0, 8).total;
-        if (h->ordinals)   // canonical ordinals for the paged documents (reloadFromSegments)
-            launch_load_convert(MTK(LC_LOG), dim3(s->n_docs), dim3(MT_WAVE), lb, h->stream, h->st,
-                               s->sc, pc, (int)s->doc_lo);
-        else
-            launch_load_convert(MTK(LC_FAST), dim3(s->n_docs), dim3(MT_WAVE), lb, h->stream, h->st,
-                               s->sc, pc, (int)s->doc_lo);
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch_load_convert(h, s, h->pg_full, false));
         const int rc = load_grow(h, s);
         if (rc) {   // (the load's events stay a pair: mt_last_load_ms reads both)
             (void)hipEventRecord(h->ev_load1, h->stream);
@@ -2755,8 +2866,8 @@ int mt_extract_snapshots(mt_handle *h, int64_t *io, mt_seg_rec *recs, uint16_t *
     const uint32_t N = h->n_docs;
     HIPCHK(h, hipSetDevice(h->device));
     SETTLE(h);
-    int64_t *d_io = nullptr;
-    HIPCHK(h, hipMalloc(&d_io, (size_t)N * 3 * 8));
+    DevBuf<int64_t> d_io;
+    HIPCHK(h, d_io.alloc((size_t)N * 3));
     const int mode = recs ? 1 : 0;
     uint64_t nr = 0, nt = 0, np = 0;
     std::vector<int64_t> off;
@@ -2771,40 +2882,32 @@ int mt_extract_snapshots(mt_handle *h, int64_t *io, mt_seg_rec *recs, uint16_t *
             np += io[3 * d + 2];
         }
     }
-    mt_seg_rec *d_recs = nullptr;
-    uint16_t *d_text = nullptr;
-    uint32_t *d_props = nullptr;
-    int32_t *d_win = nullptr;
-    bool ok = hipMalloc(&d_win, (size_t)N * 8) == hipSuccess;
-    if (ok && mode)
-        ok = hipMalloc(&d_recs, std::max<uint64_t>(nr, 1) * sizeof(mt_seg_rec)) == hipSuccess &&
-             hipMalloc(&d_text, std::max<uint64_t>(nt, 1) * 2) == hipSuccess &&
-             hipMalloc(&d_props, std::max<uint64_t>(np, 1) * 4) == hipSuccess &&
-             hipMemcpy(d_io, off.data(), (size_t)N * 3 * 8, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) {
-        hipLaunchKernelGGL(k_extract, dim3(N), dim3(MT_WAVE), 0, h->stream, h->st, mode, d_io, d_recs, d_text, d_props,
-                           d_win);
-        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
+    DevBuf<mt_seg_rec> d_recs;
+    DevBuf<uint16_t> d_text;
+    DevBuf<uint32_t> d_props;
+    DevBuf<int32_t> d_win;
+    HIPCHK(h, d_win.alloc((size_t)N * 2));
+    if (mode) {
+        HIPCHK(h, d_recs.alloc(nr));
+        HIPCHK(h, d_text.alloc(nt));
+        HIPCHK(h, d_props.alloc(np));
+        HIPCHK(h, hipMemcpy(d_io.p, off.data(), (size_t)N * 3 * 8, hipMemcpyHostToDevice));
     }
-    if (ok && !mode) ok = hipMemcpy(io, d_io, (size_t)N * 3 * 8, hipMemcpyDeviceToHost) == hipSuccess;
-    if (ok && mode) {
-        ok = (!nr || hipMemcpy(recs, d_recs, nr * sizeof(mt_seg_rec), hipMemcpyDeviceToHost) == hipSuccess) &&
-             (!nt || !text || hipMemcpy(text, d_text, nt * 2, hipMemcpyDeviceToHost) == hipSuccess) &&
-             (!np || !props || hipMemcpy(props, d_props, np * 4, hipMemcpyDeviceToHost) == hipSuccess);
+    hipLaunchKernelGGL(k_extract, dim3(N), dim3(MT_WAVE), 0, h->stream, h->st, mode, d_io.p, d_recs.p, d_text.p,
+                       d_props.p, d_win.p);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!mode) HIPCHK(h, hipMemcpy(io, d_io.p, (size_t)N * 3 * 8, hipMemcpyDeviceToHost));
+    if (mode) {
+        if (nr) HIPCHK(h, hipMemcpy(recs, d_recs.p, nr * sizeof(mt_seg_rec), hipMemcpyDeviceToHost));
+        if (nt && text) HIPCHK(h, hipMemcpy(text, d_text.p, nt * 2, hipMemcpyDeviceToHost));
+        if (np && props) HIPCHK(h, hipMemcpy(props, d_props.p, np * 4, hipMemcpyDeviceToHost));
     }
     std::vector<int32_t> win((size_t)N * 2);
-    if (ok) ok = hipMemcpy(win.data(), d_win, (size_t)N * 8, hipMemcpyDeviceToHost) == hipSuccess;
-    if (ok)
-        for (uint32_t d = 0; d < N; d++) {
-            if (min_seq) min_seq[d] = win[2 * d];
-            if (cur_seq) cur_seq[d] = win[2 * d + 1];
-        }
-    void *ps[] = {d_io, d_recs, d_text, d_props, d_win};
-    for (void *p : ps)
-        if (p) hipFree(p);
-    if (!ok) {
-        h->err = "mt_extract_snapshots failed";
-        return MT_E_HIP;
+    HIPCHK(h, hipMemcpy(win.data(), d_win.p, (size_t)N * 8, hipMemcpyDeviceToHost));
+    for (uint32_t d = 0; d < N; d++) {
+        if (min_seq) min_seq[d] = win[2 * d];
+        if (cur_seq) cur_seq[d] = win[2 * d + 1];
     }
     return 0;
 }
@@ -2839,6 +2942,97 @@ mt_batch *mt_generate(mt_handle *h, const mt_gen_cfg *cfg, uint32_t doc_index_ba
     return mt_generate_docs(h, cfg, doc_index_base, nullptr, nullptr, view_len_trace);
 }
 
+// mt_generate_docs' device work into batch b (sized by the caller, who frees it on failure and
+// clears st.gen_off / st.gen_ids, which point at buffers of this function while it runs).
+static int generate_into(mt_handle *h, mt_batch *b, mt_gen_cfg cfg, uint32_t doc_index_base, const int64_t *off,
+                         bool own_lengths, const int32_t *doc_ids, int32_t *view_len_trace) {
+    const int64_t N = h->n_docs;
+    // every document's region at fixed strides per message (gen_begin)
+    int64_t tstride = (int64_t)cfg.ops * cfg.text_max + 1;
+    int64_t pstride = (int64_t)cfg.ops * (1 + 2 * (int64_t)cfg.max_keys_per_op) + 1;
+    DevBuf<int32_t> d_fail, d_trace, d_ids;   // d_ids: the documents' global indices (their draws)
+    DevBuf<int64_t> d_used;
+    if (view_len_trace) HIPCHK(h, d_trace.alloc((size_t)b->n_ops * 4));
+    HIPCHK(h, batch_alloc(b));
+    HIPCHK(h, d_fail.alloc(N));
+    HIPCHK(h, d_used.alloc(2 * N));
+    HIPCHK(h, hipMemcpy(b->off, off, (N + 1) * 8, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemset(d_fail.p, 0, N * 4));
+    if (!set_order(b, off)) return MT_E_HIP;
+    h->st.gen_off = own_lengths ? b->off : nullptr;   // (the generator kernels' lengths)
+    if (doc_ids) {
+        HIPCHK(h, d_ids.alloc(N));
+        HIPCHK(h, hipMemcpy(d_ids.p, doc_ids, N * 4, hipMemcpyHostToDevice));
+    }
+    h->st.gen_ids = d_ids.p;
+    HIPCHK(h, hipMemsetAsync(h->st.stats, 0, MT_STATS_WORDS * sizeof(uint32_t), h->stream));
+    // k_generate / k_generate_paged: the same parameters but the last, the tier's capacities
+    const int gw = 2 * (cfg.writers + 1);
+    auto launch = [&](const Pick &p, void *caps) {
+        void *a[] = {&h->st, &cfg, &doc_index_base, &b->ops, &b->text, &b->props, &tstride, &pstride, &d_fail.p,
+                     &d_trace.p, &d_used.p, caps};
+        return launch_variant(p, h->n_docs, h->stream, a);
+    };
+    if (h->lds.S > 0) {
+        TierCaps caps = h->lds;
+        HIPCHK(h, launch(pick_flat(K_GENERATE, facts(h), caps, gw), &caps));
+    } else {
+        HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->st.retry, 1, h->n_docs, h->stream));
+    }
+    if (h->st.PP > 0) {
+        for (PagedCaps pc : {h->pg_tight, h->pg_full})
+            if (pc.PP) HIPCHK(h, launch(pick_paged(K_GENERATE_PAGED, facts(h), pc, false, gw), &pc));
+    } else {
+        TierCaps caps = glb_caps(h);
+        HIPCHK(h, launch(pick_flat(K_GENERATE, facts(h), caps, gw), &caps));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<int32_t> f(N);
+    HIPCHK(h, hipMemcpy(f.data(), d_fail.p, N * 4, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < N; i++)
+        if (f[i]) {
+            DocHdr hd;
+            hipMemcpy(&hd, h->st.hdr + i, sizeof(DocHdr), hipMemcpyDeviceToHost);
+            h->err = "mt_generate: document " + std::to_string(i) + " failed with status " + std::to_string(f[i]) +
+                     " (diagnostic " + std::to_string(hd.pad[HDR_DIAG]) + ")";
+            return MT_E_INVALID;
+        }
+    // pack the per-document regions (u32 offsets address the whole batch)
+    std::vector<int64_t> used((size_t)N * 2), base((size_t)N * 2);
+    HIPCHK(h, hipMemcpy(used.data(), d_used.p, N * 16, hipMemcpyDeviceToHost));
+    int64_t tt = 0, tp = 0;
+    for (int64_t i = 0; i < N; i++) {
+        base[2 * i] = tt;
+        base[2 * i + 1] = tp;
+        tt += used[2 * i];
+        tp += used[2 * i + 1];
+    }
+    if (tt > (int64_t)UINT32_MAX || tp >= (int64_t)MT_NO_PROPS) {
+        h->err = "mt_generate: the batch's text / property arenas exceed 32-bit offsets";
+        return MT_E_INVALID;
+    }
+    DevBuf<uint16_t> nt;
+    DevBuf<uint32_t> np;
+    DevBuf<int64_t> d_base;
+    HIPCHK(h, nt.alloc(tt));
+    HIPCHK(h, np.alloc(tp));
+    HIPCHK(h, d_base.alloc(2 * N));
+    HIPCHK(h, hipMemcpy(d_base.p, base.data(), N * 16, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_gen_compact, dim3(h->n_docs), dim3(256), 0, h->stream, b->ops, b->off, b->text, b->props,
+                       (int64_t)cfg.text_max, 1 + 2 * (int64_t)cfg.max_keys_per_op, d_used.p, d_base.p, nt.p, np.p,
+                       h->n_docs);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    hipFree(b->text);
+    hipFree(b->props);
+    b->text = nt.release();
+    b->props = np.release();
+    b->text_len = tt;
+    b->props_len = tp;
+    if (view_len_trace) HIPCHK(h, hipMemcpy(view_len_trace, d_trace.p, b->n_ops * 16, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 mt_batch *mt_generate_docs(mt_handle *h, const mt_gen_cfg *cfg, uint32_t doc_index_base,
                            const int32_t *ops_per_doc, const int32_t *doc_ids, int32_t *view_len_trace) {
     if (!h || !cfg || cfg->writers < 1 || cfg->ops < 0) return nullptr;
@@ -2856,130 +3050,16 @@ mt_batch *mt_generate_docs(mt_handle *h, const mt_gen_cfg *cfg, uint32_t doc_ind
     b->device = h->device;
     b->n_docs = h->n_docs;
     const int64_t N = h->n_docs, ops = cfg->ops;
-    // every document's region at fixed strides per message (gen_begin)
-    const int64_t tstride = ops * cfg->text_max + 1;
-    const int64_t pstride = ops * (1 + 2 * (int64_t)cfg->max_keys_per_op) + 1;
     std::vector<int64_t> off(N + 1);
     for (int64_t i = 0; i <= N; i++) off[i] = ops_per_doc ? (i ? off[i - 1] + ops_per_doc[i - 1] : 0) : i * ops;
     b->n_ops = off[N];
     b->text_len = off[N] * cfg->text_max + N;
     b->props_len = off[N] * (1 + 2 * (int64_t)cfg->max_keys_per_op) + N;
-    int32_t *d_fail = nullptr, *d_trace = nullptr;
-    int64_t *d_used = nullptr;
-    if (view_len_trace && hipMalloc(&d_trace, std::max<int64_t>(b->n_ops, 1) * 16) != hipSuccess) {
-        delete b;
-        return nullptr;
-    }
-    bool ok = hipMalloc(&b->off, (N + 1) * sizeof(int64_t)) == hipSuccess &&
-              hipMalloc(&b->ops, std::max<int64_t>(b->n_ops, 1) * sizeof(mt_op_rec)) == hipSuccess &&
-              hipMalloc(&b->text, b->text_len * 2) == hipSuccess &&
-              hipMalloc(&b->props, b->props_len * 4) == hipSuccess &&
-              hipMalloc(&d_fail, N * 4) == hipSuccess && hipMalloc(&d_used, N * 16) == hipSuccess;
-    if (ok) {
-        ok = hipMemcpy(b->off, off.data(), (N + 1) * 8, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemset(d_fail, 0, N * 4) == hipSuccess && set_order(b, off.data());
-        h->st.gen_off = ops_per_doc ? b->off : nullptr;   // (the generator kernels' lengths)
-    }
-    int32_t *d_ids = nullptr;   // the documents' global indices (their draws)
-    if (ok && doc_ids)
-        ok = hipMalloc(&d_ids, N * 4) == hipSuccess && hipMemcpy(d_ids, doc_ids, N * 4, hipMemcpyHostToDevice) == hipSuccess;
-    h->st.gen_ids = d_ids;
-    if (ok) ok = hipMemsetAsync(h->st.stats, 0, MT_STATS_WORDS * sizeof(uint32_t), h->stream) == hipSuccess;
-    if (ok) {
-        const int gw = 2 * (cfg->writers + 1);
-        if (h->lds.S > 0) {
-            launch_generate(MTK(G_LDS), dim3(h->n_docs), dim3(MT_WAVE), tier_lds_bytes(true, h->lds, gw),
-                               h->stream, h->st, *cfg, doc_index_base, b->ops, b->text, b->props, tstride,
-                               pstride, d_fail, d_trace, d_used, h->lds);
-            ok = hipGetLastError() == hipSuccess;
-        } else {
-            ok = hipMemsetD32Async((hipDeviceptr_t)h->st.retry, 1, h->n_docs, h->stream) == hipSuccess;
-        }
-        if (ok && h->st.PP > 0) {
-            const PagedCaps *tiers[2] = {h->pg_tight.PP ? &h->pg_tight : nullptr, &h->pg_full};
-            for (const PagedCaps *pc : tiers) {
-                if (!pc || !ok) continue;
-                const size_t lb = paged_layout(pc->PP, pc->PH, pc->UT, gw, pc->narrow ? 4 : 8).total;
-                if (pc->narrow)
-                    launch_generate_paged(MTK(GP_NARROW), dim3(h->n_docs), dim3(MT_WAVE), lb,
-                                       h->stream, h->st, *cfg, doc_index_base, b->ops, b->text, b->props, tstride,
-                                       pstride, d_fail, d_trace, d_used, *pc);
-                else
-                    launch_generate_paged(MTK(GP_FULL), dim3(h->n_docs), dim3(MT_WAVE), lb,
-                                       h->stream, h->st, *cfg, doc_index_base, b->ops, b->text, b->props, tstride,
-                                       pstride, d_fail, d_trace, d_used, *pc);
-                ok = hipGetLastError() == hipSuccess;
-            }
-            ok = ok && hipStreamSynchronize(h->stream) == hipSuccess;
-        } else if (ok) {
-            launch_generate(MTK(G_GLB), dim3(h->n_docs), dim3(MT_WAVE),
-                               tier_lds_bytes(false, glb_caps(h), gw), h->stream, h->st, *cfg, doc_index_base,
-                               b->ops, b->text, b->props, tstride, pstride, d_fail, d_trace, d_used, glb_caps(h));
-            ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
-        }
-    }
-    if (ok) {
-        std::vector<int32_t> f(N);
-        ok = hipMemcpy(f.data(), d_fail, N * 4, hipMemcpyDeviceToHost) == hipSuccess;
-        for (int64_t i = 0; ok && i < N; i++)
-            if (f[i]) {
-                DocHdr hd;
-                hipMemcpy(&hd, h->st.hdr + i, sizeof(DocHdr), hipMemcpyDeviceToHost);
-                h->err = "mt_generate: document " + std::to_string(i) + " failed with status " + std::to_string(f[i]) +
-                         " (diagnostic " + std::to_string(hd.pad[HDR_DIAG]) + ")";
-                ok = false;
-            }
-    }
-    if (ok) {   // pack the per-document regions (u32 offsets address the whole batch)
-        std::vector<int64_t> used((size_t)N * 2), base((size_t)N * 2);
-        ok = hipMemcpy(used.data(), d_used, N * 16, hipMemcpyDeviceToHost) == hipSuccess;
-        int64_t tt = 0, tp = 0;
-        for (int64_t i = 0; ok && i < N; i++) {
-            base[2 * i] = tt;
-            base[2 * i + 1] = tp;
-            tt += used[2 * i];
-            tp += used[2 * i + 1];
-        }
-        if (ok && (tt > (int64_t)UINT32_MAX || tp >= (int64_t)MT_NO_PROPS)) {
-            h->err = "mt_generate: the batch's text / property arenas exceed 32-bit offsets";
-            ok = false;
-        }
-        uint16_t *nt = nullptr;
-        uint32_t *np = nullptr;
-        if (ok)
-            ok = hipMalloc(&nt, std::max<int64_t>(tt, 1) * 2) == hipSuccess &&
-                 hipMalloc(&np, std::max<int64_t>(tp, 1) * 4) == hipSuccess;
-        int64_t *d_base = nullptr;
-        if (ok) ok = hipMalloc(&d_base, N * 16) == hipSuccess &&
-                     hipMemcpy(d_base, base.data(), N * 16, hipMemcpyHostToDevice) == hipSuccess;
-        if (ok) {
-            hipLaunchKernelGGL(k_gen_compact, dim3(h->n_docs), dim3(256), 0, h->stream, b->ops, b->off, b->text,
-                               b->props, (int64_t)cfg->text_max, 1 + 2 * (int64_t)cfg->max_keys_per_op, d_used,
-                               d_base, nt, np, h->n_docs);
-            ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
-        }
-        if (d_base) hipFree(d_base);
-        if (ok) {
-            hipFree(b->text);
-            hipFree(b->props);
-            b->text = nt;
-            b->props = np;
-            b->text_len = tt;
-            b->props_len = tp;
-        } else {
-            if (nt) hipFree(nt);
-            if (np) hipFree(np);
-        }
-    }
+    const int rc = generate_into(h, b, *cfg, doc_index_base, off.data(), ops_per_doc != nullptr, doc_ids,
+                                 view_len_trace);
     h->st.gen_off = nullptr;
     h->st.gen_ids = nullptr;
-    if (d_ids) hipFree(d_ids);
-    if (ok && d_trace)
-        ok = hipMemcpy(view_len_trace, d_trace, b->n_ops * 16, hipMemcpyDeviceToHost) == hipSuccess;
-    if (d_trace) hipFree(d_trace);
-    if (d_fail) hipFree(d_fail);
-    if (d_used) hipFree(d_used);
-    if (!ok) {
+    if (rc) {
         if (h->err.empty()) h->err = "mt_generate failed";
         mt_batch_free(b);
         return nullptr;
@@ -3189,116 +3269,69 @@ int mt_get_text(mt_handle *h, uint32_t doc, uint16_t *out, uint32_t cap, uint32_
     return 0;
 }
 
-// mt_get_texts / mt_get_texts_device: the counting pass, the prefix sums (on the host for host
-// results, as mt_extract_snapshots takes them; k_text_scan for device results), the gather.
-namespace {
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) hipFree(p);
-    }
-};
-}   // namespace
+// mt_get_texts / mt_get_texts_device: the counting pass, the prefix sums, the gather.
 static int get_texts(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
-                     uint16_t marker_unit, int64_t *off, uint16_t *out, void *off_dev, void *out_dev, uint64_t cap,
-                     bool device) {
-    if (!h || n > 0x7FFFFFFFu || (device ? !off_dev : !off)) return MT_E_INVALID;
-    if (!docs && n > h->n_docs) return MT_E_INVALID;
-    if (docs)
-        for (uint32_t q = 0; q < n; q++)
-            if (docs[q] >= h->n_docs) return MT_E_INVALID;
+                     uint16_t marker_unit, int64_t *off, uint16_t *out, void *out_dev, uint64_t cap, bool device) {
+    if (!h || !off) return MT_E_INVALID;
+    int rc = check_queries(h, "mt_get_texts", n, docs);
+    if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     SETTLE(h);
-    h->txt_timed = 0;
-    if (n == 0) {
-        if (device)
-            HIPCHK(h, hipMemset(off_dev, 0, 8));
-        else
-            off[0] = 0;
-        return 0;
-    }
-    for (hipEvent_t &e : h->ev_txt)
-        if (!e) HIPCHK(h, hipEventCreate(&e));
-    // one allocation: [docs | start | end] (n words each, absent ones stay unused), len[n], off[n + 1]
-    DevBuf args, d_out;
-    const size_t words = (size_t)n * 3 + (n & 1);   // (the 8-byte arrays stay aligned)
-    HIPCHK(h, hipMalloc(&args.p, words * 4 + ((size_t)n * 2 + 1) * 8));
-    uint32_t *d_docs = (uint32_t *)args.p;
-    int32_t *d_start = (int32_t *)args.p + n, *d_end = (int32_t *)args.p + 2 * (size_t)n;
-    int64_t *d_len = (int64_t *)((uint32_t *)args.p + words), *d_off = d_len + n;
-    if (docs) HIPCHK(h, hipMemcpy(d_docs, docs, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (start) HIPCHK(h, hipMemcpy(d_start, start, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (end) HIPCHK(h, hipMemcpy(d_end, end, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (!docs) d_docs = nullptr;
-    if (!start) d_start = nullptr;
-    if (!end) d_end = nullptr;
-    HIPCHK(h, hipEventRecord(h->ev_txt[0], h->stream));
+    ReadTimer &tm = h->tm_txt;
+    tm.timed = 0;
+    if (n == 0) return empty_offsets(h, {off}, device);
+    QueryCols qc;   // extra: len[n], off[n + 1]
+    HIPCHK(h, qc.upload(n, {docs, start, end}, ((size_t)n * 2 + 1) * 8));
+    const uint32_t *d_docs = (const uint32_t *)qc.col[0];
+    const int32_t *d_start = (const int32_t *)qc.col[1], *d_end = (const int32_t *)qc.col[2];
+    int64_t *d_len = (int64_t *)qc.extra, *d_off = device ? off : d_len + n;
+    HIPCHK(h, tm.begin(0, h->stream));
     hipLaunchKernelGGL(k_text_count, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start, d_end,
                        (int)marker_unit, d_len);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev_txt[1], h->stream));
+    HIPCHK(h, tm.end(0, h->stream));
     int64_t total = 0;
-    if (device) {
-        d_off = (int64_t *)off_dev;
-        hipLaunchKernelGGL(k_text_scan, dim3(1), dim3(1024), 0, h->stream, d_len, (int)n, d_off);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(&total, d_off + n, 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    } else {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipMemcpy(off + 1, d_len, (size_t)n * 8, hipMemcpyDeviceToHost));
-        off[0] = 0;
-        for (uint32_t q = 0; q < n; q++) off[q + 1] += off[q];
-        total = off[n];
-    }
-    h->txt_timed = 1;
-    if (device ? !out_dev : !out) return 0;   // sizing only
-    if (cap < (uint64_t)total) {
-        h->err = "mt_get_texts: the output holds " + std::to_string(cap) + " units, the results need " +
-                 std::to_string(total);
-        return MT_E_OVERFLOW;
-    }
-    if (total == 0) return 0;
-    uint16_t *d_text = (uint16_t *)out_dev;
-    if (!device) {
-        HIPCHK(h, hipMemcpy(d_off, off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
-        HIPCHK(h, hipMalloc(&d_out.p, (size_t)total * 2));
-        d_text = (uint16_t *)d_out.p;
-    }
+    if ((rc = scan_counts(h, n, 1, &d_len, &off, device, &total))) return rc;
+    tm.timed = 1;
+    rc = after_counts(h, device ? !out_dev : !out, cap >= (uint64_t)total, total == 0, [&] {
+        return "mt_get_texts: the output holds " + std::to_string(cap) + " units, the results need " +
+               std::to_string(total);
+    });
+    if (rc != RO_GATHER) return rc;
+    if (!device) HIPCHK(h, hipMemcpy(d_off, off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+    OutStage<uint16_t> text;
+    HIPCHK(h, text.open(out_dev, device, (size_t)total));
     // MT_TEXT_PER_SEGMENT=1: the per-segment copy (the A/B of tools/readout_probe.py)
     const char *ps = getenv("MT_TEXT_PER_SEGMENT");
     const bool per_seg = ps && ps[0] == '1';
-    HIPCHK(h, hipEventRecord(h->ev_txt[2], h->stream));
+    HIPCHK(h, tm.begin(1, h->stream));
     if (per_seg)
         hipLaunchKernelGGL(k_text_gather<true>, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start,
-                           d_end, (int)marker_unit, d_off, d_text);
+                           d_end, (int)marker_unit, d_off, text.p);
     else
         hipLaunchKernelGGL(k_text_gather<false>, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start,
-                           d_end, (int)marker_unit, d_off, d_text);
+                           d_end, (int)marker_unit, d_off, text.p);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev_txt[3], h->stream));
+    HIPCHK(h, tm.end(1, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->txt_timed = 2;
-    if (!device) HIPCHK(h, hipMemcpy(out, d_text, (size_t)total * 2, hipMemcpyDeviceToHost));
+    tm.timed = 2;
+    HIPCHK(h, text.copy_out(out, (size_t)total));
     return 0;
 }
 
 int mt_get_texts(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
                  uint16_t marker_unit, int64_t *off, uint16_t *out, uint64_t cap) {
-    return get_texts(h, n, docs, start, end, marker_unit, off, out, nullptr, nullptr, cap, false);
+    return get_texts(h, n, docs, start, end, marker_unit, off, out, nullptr, cap, false);
 }
 
 int mt_get_texts_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
                         uint16_t marker_unit, void *off_dev, void *out_dev, uint64_t cap) {
-    return get_texts(h, n, docs, start, end, marker_unit, nullptr, nullptr, off_dev, out_dev, cap, true);
+    return get_texts(h, n, docs, start, end, marker_unit, (int64_t *)off_dev, nullptr, out_dev, cap, true);
 }
 
 int mt_last_text_ms(mt_handle *h, float *out) {
     if (!h || !out) return MT_E_INVALID;
-    out[0] = out[1] = 0.f;
-    if (h->txt_timed >= 1) HIPCHK(h, hipEventElapsedTime(&out[0], h->ev_txt[0], h->ev_txt[1]));
-    if (h->txt_timed >= 2) HIPCHK(h, hipEventElapsedTime(&out[1], h->ev_txt[2], h->ev_txt[3]));
-    return 0;
+    return read_timer(h, h->tm_txt, out);
 }
 
 // mt_get_prop_runs_bulk / mt_get_prop_runs_bulk_device: get_texts' shape with two counts per
@@ -3306,98 +3339,52 @@ int mt_last_text_ms(mt_handle *h, float *out) {
 static int get_prop_runs_bulk(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start,
                               const int32_t *end, int64_t *run_off, int64_t *word_off, void *runs, uint64_t cap_runs,
                               void *records, uint64_t cap_words, bool device) {
-    if (!h || n > 0x7FFFFFFFu || !run_off || !word_off) return MT_E_INVALID;
-    if (!docs && n > h->n_docs) return MT_E_INVALID;
-    if (docs)
-        for (uint32_t q = 0; q < n; q++)
-            if (docs[q] >= h->n_docs) return MT_E_INVALID;
+    if (!h || !run_off || !word_off) return MT_E_INVALID;
+    int rc = check_queries(h, "mt_get_prop_runs_bulk", n, docs);
+    if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     SETTLE(h);
-    h->prp_timed = 0;
-    if (n == 0) {
-        if (device) {
-            HIPCHK(h, hipMemset(run_off, 0, 8));
-            HIPCHK(h, hipMemset(word_off, 0, 8));
-        } else {
-            run_off[0] = word_off[0] = 0;
-        }
-        return 0;
-    }
-    for (hipEvent_t &e : h->ev_prp)
-        if (!e) HIPCHK(h, hipEventCreate(&e));
-    // one allocation: [docs | start | end] (n words each, absent ones stay unused), the run and
-    // word counts [n] each, the two offset arrays [n + 1] each
-    DevBuf args, d_runs, d_recs;
-    const size_t words = (size_t)n * 3 + (n & 1);   // (the 8-byte arrays stay aligned)
-    HIPCHK(h, hipMalloc(&args.p, words * 4 + ((size_t)n * 4 + 2) * 8));
-    uint32_t *d_docs = (uint32_t *)args.p;
-    int32_t *d_start = (int32_t *)args.p + n, *d_end = (int32_t *)args.p + 2 * (size_t)n;
-    int64_t *d_nr = (int64_t *)((uint32_t *)args.p + words), *d_nw = d_nr + n;
-    int64_t *d_roff = d_nw + n, *d_woff = d_roff + n + 1;
-    if (docs) HIPCHK(h, hipMemcpy(d_docs, docs, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (start) HIPCHK(h, hipMemcpy(d_start, start, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (end) HIPCHK(h, hipMemcpy(d_end, end, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (!docs) d_docs = nullptr;
-    if (!start) d_start = nullptr;
-    if (!end) d_end = nullptr;
-    HIPCHK(h, hipEventRecord(h->ev_prp[0], h->stream));
+    ReadTimer &tm = h->tm_prp;
+    tm.timed = 0;
+    if (n == 0) return empty_offsets(h, {run_off, word_off}, device);
+    QueryCols qc;   // extra: the run and word counts [n] each, the two offset arrays [n + 1] each
+    HIPCHK(h, qc.upload(n, {docs, start, end}, ((size_t)n * 4 + 2) * 8));
+    const uint32_t *d_docs = (const uint32_t *)qc.col[0];
+    const int32_t *d_start = (const int32_t *)qc.col[1], *d_end = (const int32_t *)qc.col[2];
+    int64_t *d_cnt[2] = {(int64_t *)qc.extra, (int64_t *)qc.extra + n};   // runs, words
+    int64_t *off[2] = {run_off, word_off};
+    int64_t *d_roff = device ? run_off : d_cnt[1] + n, *d_woff = device ? word_off : d_roff + n + 1;
+    HIPCHK(h, tm.begin(0, h->stream));
     hipLaunchKernelGGL(k_props_count, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start, d_end,
-                       d_nr, d_nw);
+                       d_cnt[0], d_cnt[1]);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev_prp[1], h->stream));
-    int64_t total_r = 0, total_w = 0;
-    if (device) {
-        d_roff = run_off;
-        d_woff = word_off;
-        hipLaunchKernelGGL(k_text_scan, dim3(1), dim3(1024), 0, h->stream, d_nr, (int)n, d_roff);
-        HIPCHK(h, hipGetLastError());
-        hipLaunchKernelGGL(k_text_scan, dim3(1), dim3(1024), 0, h->stream, d_nw, (int)n, d_woff);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(&total_r, d_roff + n, 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(&total_w, d_woff + n, 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    } else {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipMemcpy(run_off + 1, d_nr, (size_t)n * 8, hipMemcpyDeviceToHost));
-        HIPCHK(h, hipMemcpy(word_off + 1, d_nw, (size_t)n * 8, hipMemcpyDeviceToHost));
-        run_off[0] = word_off[0] = 0;
-        for (uint32_t q = 0; q < n; q++) {
-            run_off[q + 1] += run_off[q];
-            word_off[q + 1] += word_off[q];
-        }
-        total_r = run_off[n];
-        total_w = word_off[n];
-    }
-    h->prp_timed = 1;
-    if (!runs) return 0;   // sizing only
+    HIPCHK(h, tm.end(0, h->stream));
+    int64_t total[2] = {0, 0};
+    if ((rc = scan_counts(h, n, 2, d_cnt, off, device, total))) return rc;
+    tm.timed = 1;
     if (!records) cap_words = 0;
-    if (cap_runs < (uint64_t)total_r || cap_words < (uint64_t)total_w) {
-        h->err = "mt_get_prop_runs_bulk: the outputs hold " + std::to_string(cap_runs) + " runs and " +
-                 std::to_string(cap_words) + " words, the results need " + std::to_string(total_r) + " runs and " +
-                 std::to_string(total_w) + " words";
-        return MT_E_OVERFLOW;
-    }
-    if (total_r == 0) return 0;
-    uint32_t *g_runs = (uint32_t *)runs, *g_recs = (uint32_t *)records;
+    rc = after_counts(h, !runs, cap_runs >= (uint64_t)total[0] && cap_words >= (uint64_t)total[1], total[0] == 0, [&] {
+        return "mt_get_prop_runs_bulk: the outputs hold " + std::to_string(cap_runs) + " runs and " +
+               std::to_string(cap_words) + " words, the results need " + std::to_string(total[0]) + " runs and " +
+               std::to_string(total[1]) + " words";
+    });
+    if (rc != RO_GATHER) return rc;
     if (!device) {
         HIPCHK(h, hipMemcpy(d_roff, run_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
         HIPCHK(h, hipMemcpy(d_woff, word_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
-        HIPCHK(h, hipMalloc(&d_runs.p, (size_t)total_r * 12));
-        HIPCHK(h, hipMalloc(&d_recs.p, (size_t)std::max<int64_t>(total_w, 1) * 4));
-        g_runs = (uint32_t *)d_runs.p;
-        g_recs = (uint32_t *)d_recs.p;
     }
-    HIPCHK(h, hipEventRecord(h->ev_prp[2], h->stream));
+    OutStage<uint32_t> g_runs, g_recs;   // a run is three words
+    HIPCHK(h, g_runs.open(runs, device, (size_t)total[0] * 3));
+    HIPCHK(h, g_recs.open(records, device, (size_t)total[1]));
+    HIPCHK(h, tm.begin(1, h->stream));
     hipLaunchKernelGGL(k_props_gather, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start, d_end,
-                       d_roff, d_woff, g_runs, g_recs);
+                       d_roff, d_woff, g_runs.p, g_recs.p);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev_prp[3], h->stream));
+    HIPCHK(h, tm.end(1, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->prp_timed = 2;
-    if (!device) {
-        HIPCHK(h, hipMemcpy(runs, g_runs, (size_t)total_r * 12, hipMemcpyDeviceToHost));
-        if (total_w) HIPCHK(h, hipMemcpy(records, g_recs, (size_t)total_w * 4, hipMemcpyDeviceToHost));
-    }
+    tm.timed = 2;
+    HIPCHK(h, g_runs.copy_out(runs, (size_t)total[0] * 3));
+    HIPCHK(h, g_recs.copy_out(records, (size_t)total[1]));
     return 0;
 }
 
@@ -3416,10 +3403,7 @@ int mt_get_prop_runs_bulk_device(mt_handle *h, uint32_t n, const uint32_t *docs,
 
 int mt_last_props_ms(mt_handle *h, float *out) {
     if (!h || !out) return MT_E_INVALID;
-    out[0] = out[1] = 0.f;
-    if (h->prp_timed >= 1) HIPCHK(h, hipEventElapsedTime(&out[0], h->ev_prp[0], h->ev_prp[1]));
-    if (h->prp_timed >= 2) HIPCHK(h, hipEventElapsedTime(&out[1], h->ev_prp[2], h->ev_prp[3]));
-    return 0;
+    return read_timer(h, h->tm_prp, out);
 }
 
 int mt_get_prop_runs(mt_handle *h, uint32_t doc, uint32_t *runs, uint32_t cap_runs,
@@ -3796,47 +3780,36 @@ enum { LOC_POS = 0, LOC_UID = 1, LOC_LEN = 2 };
 static int locate(mt_handle *h, const char *name, int mode, uint32_t n, const uint32_t *docs, const int32_t *key,
                   const int32_t *ref_seq, const int32_t *client, mt_seg_hit *out, void *out_dev, bool device,
                   std::vector<int4> *aux_out) {
-    if (!h || n > 0x7FFFFFFFu) return MT_E_INVALID;
+    if (!h) return MT_E_INVALID;
     if (n && mode != LOC_LEN && (!key || (device ? !out_dev : !out))) return MT_E_INVALID;
     if ((ref_seq == nullptr) != (client == nullptr)) return MT_E_INVALID;
-    if (!docs && n > h->n_docs) return MT_E_INVALID;
-    for (uint32_t q = 0; q < n; q++) {
-        if (docs && docs[q] >= h->n_docs) {
-            h->err = std::string(name) + ": query " + std::to_string(q) + ": no document " + std::to_string(docs[q]);
-            return MT_E_INVALID;
-        }
-        if (mode == LOC_POS && key[q] < 0) {
+    const int bad = check_queries(h, name, n, docs);
+    if (bad) return bad;
+    for (uint32_t q = 0; mode == LOC_POS && q < n; q++)
+        if (key[q] < 0) {
             h->err = std::string(name) + ": query " + std::to_string(q) + ": negative position";
             return MT_E_INVALID;
         }
-    }
     HIPCHK(h, hipSetDevice(h->device));
     SETTLE(h);
-    h->loc_timed = false;
+    ReadTimer &tm = h->tm_loc;
+    tm.timed = 0;
     h->loc_n = n;
     h->loc_host = 0;
     if (aux_out) aux_out->clear();
     if (n == 0) return 0;
-    for (hipEvent_t &e : h->ev_loc)
-        if (!e) HIPCHK(h, hipEventCreate(&e));
-    // one allocation: aux[n] (16 bytes each), the records (host results), [docs | key | ref_seq | client]
-    DevBuf buf;
+    QueryCols qc;   // extra: aux[n] (16 bytes each), the records (host results)
     const size_t aux_b = (size_t)n * sizeof(int4), hit_b = mode != LOC_LEN && !device ? (size_t)n * sizeof(mt_seg_hit) : 0;
-    HIPCHK(h, hipMalloc(&buf.p, aux_b + hit_b + (size_t)n * 16));
-    v4i *d_aux = (v4i *)buf.p;
-    mt_seg_hit *d_hit = device ? (mt_seg_hit *)out_dev : (mt_seg_hit *)((char *)buf.p + aux_b);
-    uint32_t *d_docs = (uint32_t *)((char *)buf.p + aux_b + hit_b);
-    int32_t *d_key = (int32_t *)d_docs + n, *d_ref = d_key + n, *d_cli = d_ref + n;
-    if (docs) HIPCHK(h, hipMemcpy(d_docs, docs, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (key) HIPCHK(h, hipMemcpy(d_key, key, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (ref_seq) HIPCHK(h, hipMemcpy(d_ref, ref_seq, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (client) HIPCHK(h, hipMemcpy(d_cli, client, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (!docs) d_docs = nullptr;
-    if (!ref_seq) d_ref = d_cli = nullptr;
+    HIPCHK(h, qc.upload(n, {docs, key, ref_seq, client}, aux_b + hit_b));
+    v4i *d_aux = (v4i *)qc.extra;
+    mt_seg_hit *d_hit = device ? (mt_seg_hit *)out_dev : (mt_seg_hit *)(qc.extra + aux_b);
+    const uint32_t *d_docs = (const uint32_t *)qc.col[0];
+    const int32_t *d_key = (const int32_t *)qc.col[1], *d_ref = (const int32_t *)qc.col[2],
+                  *d_cli = (const int32_t *)qc.col[3];
     // MT_LOCATE_ROW_WALK=1: observer-view queries walk every row (the A/B of tools/cursor_probe.py)
     const char *rw = getenv("MT_LOCATE_ROW_WALK");
     const int skip = !(rw && rw[0] == '1');
-    HIPCHK(h, hipEventRecord(h->ev_loc[0], h->stream));
+    HIPCHK(h, tm.begin(0, h->stream));
     if (mode == LOC_POS)
         hipLaunchKernelGGL(k_locate<0>, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_key, d_ref, d_cli,
                            skip, d_hit, d_aux);
@@ -3847,9 +3820,9 @@ static int locate(mt_handle *h, const char *name, int mode, uint32_t n, const ui
         hipLaunchKernelGGL(k_locate<2>, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_key, d_ref, d_cli,
                            skip, (mt_seg_hit *)nullptr, d_aux);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev_loc[1], h->stream));
+    HIPCHK(h, tm.end(0, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->loc_timed = true;
+    tm.timed = 1;
     std::vector<int4> aux(n);
     HIPCHK(h, hipMemcpy(aux.data(), d_aux, aux_b, hipMemcpyDeviceToHost));
     for (uint32_t q = 0; q < n; q++)
@@ -3974,9 +3947,11 @@ int mt_last_locate(mt_handle *h, int64_t *out, float *ms) {
     if (!h || !out) return MT_E_INVALID;
     out[0] = h->loc_n;
     out[1] = h->loc_host;
+    float t[2] = {0.f, 0.f};
     if (ms) {
-        *ms = 0.f;
-        if (h->loc_timed) HIPCHK(h, hipEventElapsedTime(ms, h->ev_loc[0], h->ev_loc[1]));
+        const int rc = read_timer(h, h->tm_loc, t);
+        *ms = t[0];
+        if (rc) return rc;
     }
     return 0;
 }
@@ -4133,6 +4108,28 @@ int mt_delta_log_reset(mt_handle *h) {
 
 // Debug: section timers of an MT_PROF build (s_memtime ticks [0, 64) and call / event counts
 // [64, 128)).
+int mt_debug_pick(const mt_pick_query *q, char *name, uint32_t name_cap, uint64_t *lds_bytes) {
+    if (!q || !name || !name_cap || !lds_bytes) return MT_E_INVALID;
+    const HandleFacts f{q->delta_log != 0, q->ordinals != 0, q->live != 0, q->wpg};
+    const TierCaps lds{q->S, q->B, q->H, 0, 0}, hbm{0, q->B, 0, 0, 0};
+    const PagedCaps pc{q->PP, q->PH, q->UT, 0, 0, q->narrow, q->grow, q->packed};
+    Pick p{nullptr, 0};
+    switch (q->launch) {
+    case MT_PICK_REPLAY_LDS: p = pick_flat(K_REPLAY, f, lds, 0); break;
+    case MT_PICK_REPLAY_HBM: p = pick_flat(K_REPLAY, f, hbm, 0); break;
+    case MT_PICK_REPLAY_PAGED: p = pick_paged(K_REPLAY_PAGED, f, pc, q->big != 0, 0); break;
+    case MT_PICK_GENERATE_LDS: p = pick_flat(K_GENERATE, f, lds, q->gen_words); break;
+    case MT_PICK_GENERATE_HBM: p = pick_flat(K_GENERATE, f, hbm, q->gen_words); break;
+    case MT_PICK_GENERATE_PAGED: p = pick_paged(K_GENERATE_PAGED, f, pc, false, q->gen_words); break;
+    case MT_PICK_LOAD_CONVERT: p = pick_paged(K_LOAD_CONVERT, f, pc, q->big != 0, 0); break;
+    case MT_PICK_OCCUPANCY: p = pick_paged(K_REPLAY_PAGED, f, pc, false, 0, true); break;
+    }
+    if (!p.v) return MT_E_INVALID;
+    snprintf(name, name_cap, "%s", p.v->name);
+    *lds_bytes = p.lds;
+    return 0;
+}
+
 int mt_debug_prof(mt_handle *h, uint64_t *out, int reset) {
 #ifdef MT_PROF
     if (!h || !h->st.prof) return MT_E_INVALID;
@@ -4189,21 +4186,25 @@ int mt_regenerate_pending(mt_handle *h, uint32_t doc, mt_regen_rec *out, uint32_
     }
     HIPCHK(h, hipSetDevice(h->device));
     SETTLE(h);
-    mt_regen_rec *d_out = nullptr;
-    uint16_t *d_text = nullptr;
-    uint32_t *d_props = nullptr;
-    int32_t *d_io = nullptr;
-    bool ok = hipMalloc(&d_out, std::max<size_t>(cap, 1) * sizeof(mt_regen_rec)) == hipSuccess &&
-              hipMalloc(&d_text, std::max<size_t>(text_cap, 1) * 2) == hipSuccess &&
-              hipMalloc(&d_props, std::max<size_t>(props_cap, 1) * 4) == hipSuccess &&
-              hipMalloc(&d_io, 16) == hipSuccess;
+    DevBuf<mt_regen_rec> d_out;
+    DevBuf<uint16_t> d_text;
+    DevBuf<uint32_t> d_props;
+    DevBuf<int32_t> d_io;
+    HIPCHK(h, d_out.alloc(cap));
+    HIPCHK(h, d_text.alloc(text_cap));
+    HIPCHK(h, d_props.alloc(props_cap));
+    HIPCHK(h, d_io.alloc(4));
     int32_t io[4] = {0, 0, 0, 0};
-    for (int round = 0; ok && round < 8; round++) {
-        hipLaunchKernelGGL(k_regen, dim3(1), dim3(MT_WAVE), tier_lds_bytes(false, glb_caps(h), 0), h->stream, h->st,
-                           (int)doc, d_out, (int)cap, d_text, (int)text_cap, d_props, (int)props_cap, d_io);
-        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess &&
-             hipMemcpy(io, d_io, 16, hipMemcpyDeviceToHost) == hipSuccess;
-        if (!ok || io[0] != -5) break;
+    for (int round = 0; round < 8; round++) {
+        // the flat HBM tier's LDS (the B-tree counts), which the live growth step can raise
+        const size_t lds = lds_layout(false, 0, h->st.B, 0, 0).total;
+        HIPCHK(h, raise_lds_limit((const void *)k_regen, lds));
+        hipLaunchKernelGGL(k_regen, dim3(1), dim3(MT_WAVE), lds, h->stream, h->st, (int)doc, d_out.p, (int)cap,
+                           d_text.p, (int)text_cap, d_props.p, (int)props_cap, d_io.p);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(io, d_io.p, 16, hipMemcpyDeviceToHost));
+        if (io[0] != -5) break;
         // more segment groups than the handle's ring holds (nothing changed yet): grow it
         const int lg2 = std::min(65535, std::max(2 * h->st.LG, io[1]));
         if (lg2 <= h->st.LG || live_regrow(h, h->st.S, h->st.B, h->st.H, h->st.T, h->st.P, lg2) != 0) {
@@ -4211,17 +4212,10 @@ int mt_regenerate_pending(mt_handle *h, uint32_t doc, mt_regen_rec *out, uint32_
             break;
         }
     }
-    if (ok) {
-        if (io[0] > 0)
-            ok = hipMemcpy(out, d_out, (size_t)io[0] * sizeof(mt_regen_rec), hipMemcpyDeviceToHost) == hipSuccess &&
-                 (io[1] == 0 || hipMemcpy(out_text, d_text, (size_t)io[1] * 2, hipMemcpyDeviceToHost) == hipSuccess) &&
-                 (io[2] == 0 || hipMemcpy(out_props, d_props, (size_t)io[2] * 4, hipMemcpyDeviceToHost) == hipSuccess);
-    }
-    for (void *p : {(void *)d_out, (void *)d_text, (void *)d_props, (void *)d_io})
-        if (p) hipFree(p);
-    if (!ok) {
-        h->err = "mt_regenerate_pending: device allocation / launch failed";
-        return MT_E_HIP;
+    if (io[0] > 0) {
+        HIPCHK(h, hipMemcpy(out, d_out.p, (size_t)io[0] * sizeof(mt_regen_rec), hipMemcpyDeviceToHost));
+        if (io[1]) HIPCHK(h, hipMemcpy(out_text, d_text.p, (size_t)io[1] * 2, hipMemcpyDeviceToHost));
+        if (io[2]) HIPCHK(h, hipMemcpy(out_props, d_props.p, (size_t)io[2] * 4, hipMemcpyDeviceToHost));
     }
     if (io[0] == -3) {
         h->err = "mt_regenerate_pending: the document has failed";

@@ -489,6 +489,29 @@ int mt_last_locate(mt_handle *h, int64_t *out /* [2] */, float *ms);
 /* Debug: raw segment records (8 u32 per segment: segA then segB) and the 32-word header. */
 int mt_debug_raw(mt_handle *h, uint32_t doc, uint32_t *rows, uint32_t cap_rows, uint32_t *n_rows,
                  int32_t *hdr_words);
+/* Debug: which kernel variant (csrc/mt_variants.h) a described launch runs and the dynamic LDS
+   bytes it is given -- the library's own choice, answered without a device.  launch names the
+   launch site; the handle facts are delta_log (delta_log_capacity > 0), ordinals
+   (segment_ordinals), live (live_client) and wpg (documents per workgroup asked of the LDS
+   tier); S / B / H are the flat tier's LDS capacities (the HBM tier reads B only), PP / PH / UT /
+   narrow / packed the paged launch's, big: the growth step's region, gen_words: the generator's
+   LDS words (2 * (writers + 1)).  MT_E_INVALID: the library has no kernel for that launch. */
+#define MT_PICK_REPLAY_LDS 0     /* mt_batch_apply_async: the LDS tier */
+#define MT_PICK_REPLAY_HBM 1     /* ... the flat HBM tier (and the live growth step's rounds) */
+#define MT_PICK_REPLAY_PAGED 2   /* ... a paged tier (and the growth step's rounds: big) */
+#define MT_PICK_GENERATE_LDS 3   /* mt_generate: the LDS tier */
+#define MT_PICK_GENERATE_HBM 4
+#define MT_PICK_GENERATE_PAGED 5
+#define MT_PICK_LOAD_CONVERT 6   /* mt_snapshots_load_async: staged headers -> paged documents */
+#define MT_PICK_OCCUPANCY 7      /* mt_create: the kernel whose occupancy sizes paged_slices */
+typedef struct mt_pick_query {
+    int32_t launch; /* MT_PICK_* */
+    int32_t delta_log, ordinals, live, wpg;
+    int32_t big, gen_words;
+    int32_t S, B, H;
+    int32_t PP, PH, UT, narrow, packed, grow; /* PagedCaps */
+} mt_pick_query;
+int mt_debug_pick(const mt_pick_query *q, char *name, uint32_t name_cap, uint64_t *lds_bytes);
 /* Debug: section timers of a build with -DMT_PROF (MT_E_INVALID otherwise). */
 int mt_debug_prof(mt_handle *h, uint64_t *out /* [128] */, int reset);
 /* Debug (flat documents): the zamboni heap in array order ({maxSeq, leaf index of its segment

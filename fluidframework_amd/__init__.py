@@ -896,6 +896,75 @@ class MergeTreeBatch:
         """Empties every document's delta log (after its records were consumed)."""
         self._check(self.lib.mt_delta_log_reset(self.h), "mt_delta_log_reset")
 
+    # bulk delta-log drain (mt_get_delta_logs): get_delta_log for many documents in one counting
+    # pass and one gather on the device, optionally with one row per delta segment
+    def _dlog_queries(self, docs, from_word):
+        if docs is not None:
+            docs = np.ascontiguousarray(docs, dtype=np.uint32).reshape(-1)
+        n = len(docs) if docs is not None else self.n_docs
+        if from_word is not None:
+            from_word = np.ascontiguousarray(np.broadcast_to(np.asarray(from_word, dtype=np.int32), (n,)))
+        return n, docs, from_word
+
+    def get_delta_logs(self, docs=None, from_word=None, ranges=False):
+        """(off, words, flags) -- with ranges, (off, words, row_off, rows, flags): query q's words
+        are words[off[q]:off[q + 1]], the log of document docs[q] (every document when docs is
+        None) from word from_word[q] (None: 0) on; rows[row_off[q]:row_off[q + 1]] are its delta
+        segments (_native.DELTA_RANGE_DTYPE).  An overflowed document does not raise: flags[q]
+        carries _native.MT_DLOG_OVERFLOWED (MT_DLOG_PAST: from_word beyond the log; MT_DLOG_BAD:
+        from_word not a record boundary, no rows)."""
+        n, docs, from_word = self._dlog_queries(docs, from_word)
+        off = np.zeros(n + 1, dtype=np.int64)
+        row_off = np.zeros(n + 1, dtype=np.int64) if ranges else None
+        flags = np.zeros(max(n, 1), dtype=np.uint32)
+        args = (self.h, n, _native.ptr(docs), _native.ptr(from_word), _native.ptr(off), _native.ptr(row_off),
+                _native.ptr(flags))
+        self._check(self.lib.mt_get_delta_logs(*args, None, 0, None, 0), "mt_get_delta_logs")
+        nw, nr = int(off[n]), int(row_off[n]) if ranges else 0
+        words = np.zeros(max(nw, 1), dtype=np.int32)
+        rows = np.zeros(max(nr, 1), dtype=_native.DELTA_RANGE_DTYPE) if ranges else None
+        self._check(self.lib.mt_get_delta_logs(*args, _native.ptr(words), nw, _native.ptr(rows), nr),
+                    "mt_get_delta_logs")
+        if ranges:
+            return off, words[:nw], row_off, rows[:nr], flags[:n]
+        return off, words[:nw], flags[:n]
+
+    def get_delta_logs_device(self, docs=None, from_word=None, ranges=False):
+        """get_delta_logs with the results left on the handle's device: torch tensors off (int64
+        [n + 1]), words (int32), with ranges row_off (int64 [n + 1]) and rows (int32 [R, 8], the
+        words of mt_delta_range), and flags (int32 [n] holding the uint32 flags).  (torch is
+        imported before the first handle is created, as for get_texts_device.)"""
+        import torch
+        n, docs, from_word = self._dlog_queries(docs, from_word)
+        dev = torch.device("cuda", self.device)
+        off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        row_off = torch.empty(n + 1, dtype=torch.int64, device=dev) if ranges else None
+        flags = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        args = (self.h, n, _native.ptr(docs), _native.ptr(from_word), ctypes.c_void_p(off.data_ptr()),
+                ctypes.c_void_p(row_off.data_ptr()) if ranges else None, ctypes.c_void_p(flags.data_ptr()))
+        self._check(self.lib.mt_get_delta_logs_device(*args, None, 0, None, 0), "mt_get_delta_logs_device")
+        nw, nr = int(off[n]), int(row_off[n]) if ranges else 0
+        words = torch.empty(max(nw, 1), dtype=torch.int32, device=dev)
+        rows = torch.empty((max(nr, 1), _native.DELTA_RANGE_DTYPE.itemsize // 4), dtype=torch.int32, device=dev)
+        self._check(self.lib.mt_get_delta_logs_device(*args, ctypes.c_void_p(words.data_ptr()), nw,
+                                                      ctypes.c_void_p(rows.data_ptr()) if ranges else None, nr),
+                    "mt_get_delta_logs_device")
+        if ranges:
+            return off, words[:nw], row_off, rows[:nr], flags[:n]
+        return off, words[:nw], flags[:n]
+
+    def delta_log_reset_docs(self, docs):
+        """delta_log_reset for the listed documents only (the others keep their records)."""
+        docs = np.ascontiguousarray(docs, dtype=np.uint32).reshape(-1)
+        self._check(self.lib.mt_delta_log_reset_docs(self.h, len(docs), _native.ptr(docs)), "mt_delta_log_reset_docs")
+
+    def last_dlog_ms(self):
+        """Device time (ms) of the last get_delta_logs call's counting pass (with the walk of the
+        records when rows were asked for) and gather."""
+        out = np.zeros(2, dtype=np.float32)
+        self._check(self.lib.mt_last_dlog_ms(self.h, _native.ptr(out)), "mt_last_dlog_ms")
+        return float(out[0]), float(out[1])
+
     def maintenance_counts(self):
         """[n_docs, 3] SPLIT / APPEND / UNLINK mergeTreeMaintenanceCallback event counts
         (needs delta_log_capacity > 0)."""

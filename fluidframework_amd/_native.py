@@ -51,6 +51,11 @@ SEG_HIT_DTYPE = np.dtype([("row", "<i4"), ("uid", "<u4"), ("position", "<i4"), (
                           ("flags", "<u4")])
 MT_HIT_HOST = 1
 
+# mt_delta_range (include/mt_replay.h): one delta segment of mt_get_delta_logs' rows
+DELTA_RANGE_DTYPE = np.dtype([("query", "<i4"), ("record", "<i4"), ("seq", "<i4"), ("kind", "<i4"),
+                              ("position", "<i4"), ("length", "<i4"), ("word", "<i4"), ("uid", "<u4")])
+MT_DLOG_OVERFLOWED, MT_DLOG_PAST, MT_DLOG_BAD = 1, 2, 4
+
 
 class MtGenCfg(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint32), ("ops", ctypes.c_int32), ("writers", ctypes.c_int32),
@@ -137,6 +142,10 @@ SIGNATURES = [
     ("mt_get_overlap_arena", _I, [_P, _U32, _P]),
     ("mt_get_delta_log", _I, [_P, _U32, _P, _U32, _P]),
     ("mt_delta_log_reset", _I, [_P]),
+    ("mt_get_delta_logs", _I, [_P, _U32, _P, _P, _P, _P, _P, _P, _U64, _P, _U64]),
+    ("mt_get_delta_logs_device", _I, [_P, _U32, _P, _P, _P, _P, _P, _P, _U64, _P, _U64]),
+    ("mt_delta_log_reset_docs", _I, [_P, _U32, _P]),
+    ("mt_last_dlog_ms", _I, [_P, _P]),
     ("mt_debug_raw", _I, [_P, _U32, _P, _U32, _P, _P]),
     ("mt_debug_pick", _I, [_P, _P, _U32, _P]),
     ("mt_debug_prof", _I, [_P, _P, _I]),

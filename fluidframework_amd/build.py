@@ -10,8 +10,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "mt_replay.hip")
 VARIANTS_H = os.path.join(HERE, "csrc", "mt_variants.h")
-DEPS = [os.path.join(HERE, "csrc", f) for f in ("mt_replay.hip", "mt_engine.h", "mt_device.h", "mt_paged.h",
-                                                 "mt_kernels.h", "mt_variants.h")] + [
+DEPS = [os.path.join(HERE, "csrc", f) for f in ("mt_replay.hip", "mt_dlog.h", "mt_engine.h", "mt_device.h",
+                                                 "mt_paged.h", "mt_kernels.h", "mt_variants.h")] + [
     os.path.join(os.path.dirname(HERE), "include", f) for f in ("mt_replay.h", "mt_types.h")]
 OBJ_DIR = os.path.join(HERE, "_build")
 OUT = os.environ.get("MT_OUT") or os.path.join(HERE, "libmtreplay.so")
@@ -28,8 +28,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno
 # them; MT_SINGLE_TU=1 builds ignore them.
 VARIANT_DEFINES = {}
 
-# what the kernel instantiations (mtk_*.o) compile from: not mt_replay.hip's host code
-KERNEL_DEPS = [p for p in DEPS if not p.endswith("mt_replay.hip")]
+# what the kernel instantiations (mtk_*.o) compile from: not mt_replay.hip's host code and read-out
+# kernels (mt_dlog.h is included there only)
+KERNEL_DEPS = [p for p in DEPS if not p.endswith(("mt_replay.hip", "mt_dlog.h"))]
 
 
 def _fresh(obj, deps):

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/mt_replay.h"
+#include "mt_dlog.h"
 #include "mt_kernels.h"
 #include "mt_variants.h"
 #ifdef MT_SINGLE_TU
@@ -797,6 +798,111 @@ __global__ void __launch_bounds__(MT_WAVE) k_props_gather(DevState st, int nq, c
     if (open_row >= 0 && open_row < room_r && lane() == 0) rows[3 * open_row + 1] = (uint32_t)(Q.s + done - open_pos);
 }
 
+// ---------------------------------------------------------------- bulk delta-log read-out
+// mt_get_delta_log for many (doc, from_word) queries, and the rows of mt_delta_range: one wave
+// per query.  A query's span is its document's log from from_word to the word count (clamped
+// into [0, DL] as mt_get_delta_log clamps it), so nothing outside the document's own log is
+// read.  The records are variable-length and each header tells where the next one starts, so
+// the walk (mt_dlog.h) is serial per query: every lane of the wave runs it on the same
+// wave-uniform addresses (one cache line per load, no divergence) and lane 0 stores the rows;
+// the queries are the parallelism.
+static_assert(sizeof(mt_delta_range) == 32, "mt_delta_range size");
+struct DlogSpan {
+    const int32_t *src;
+    int words;
+    uint32_t flags;
+};
+__device__ __forceinline__ DlogSpan dlog_span(const DevState &st, int q, const uint32_t *docs, const int32_t *from) {
+    // (the host refuses doc >= n_docs and from_word < 0; a query that held one anyway reads nothing)
+    const uint32_t dq = docs ? docs[q] : (uint32_t)q;
+    const bool known = dq < (uint32_t)st.n_docs;
+    const uint32_t doc = known ? dq : 0u;
+    const int f = max(from ? from[q] : 0, 0);
+    const int have = known ? min(max(st.hdr[doc].dlog_n, 0), st.DL) : 0;
+    DlogSpan s;
+    s.flags = st.hdr[doc].pad[HDR_DLOG_OVF] ? MT_DLOG_OVERFLOWED : 0u;
+    if (f > have) s.flags |= MT_DLOG_PAST;
+    s.words = f > have ? 0 : have - f;
+    s.src = st.dlog + (size_t)doc * st.DL + min(f, have);
+    return s;
+}
+__global__ void __launch_bounds__(MT_WAVE) k_dlog_count(DevState st, int nq, const uint32_t *docs, const int32_t *from,
+                                                        int want_rows, int64_t *n_words, int64_t *n_rows,
+                                                        uint32_t *flags) {
+    const int q = blockIdx.x;
+    if (q >= nq) return;
+    DlogSpan s = dlog_span(st, q, docs, from);
+    int64_t rows = 0;
+    if (want_rows && s.words > 0) {
+        mt_dlog_count c;
+        if (mt_dlog_walk(s.src, s.words, st.DLR != 0, c))
+            rows = c.n;
+        else
+            s.flags |= MT_DLOG_BAD;
+    }
+    if (lane() == 0) {
+        n_words[q] = s.words;
+        if (want_rows) n_rows[q] = rows;
+        flags[q] = s.flags;
+    }
+}
+// n words from src to dst, V words per access in the body: the caller picks the widest V at
+// which src and dst are congruent, the head runs to dst's first V-word boundary (so src's too)
+// and the tail takes what is left; both are shorter than V words.
+template <int V> __device__ __forceinline__ void dlog_copy(int32_t *dst, const int32_t *src, int n) {
+    typedef int32_t vec __attribute__((ext_vector_type(V)));
+    const int head = min(n, (int)((V - (int)(((uintptr_t)dst >> 2) % V)) % V));
+    if (lane() < head) dst[lane()] = src[lane()];
+    const int nv = (n - head) / V;
+    const vec *s = (const vec *)(src + head);
+    vec *d = (vec *)(dst + head);
+    for (int i = lane(); i < nv; i += MT_WAVE) d[i] = s[i];
+    const int done = head + nv * V;
+    if (lane() < n - done) dst[done + lane()] = src[done + lane()];
+}
+struct DlogFill {   // the walk's sink of the fill pass: lane 0 stores, rows beyond the query's slots are dropped
+    mt_delta_range *rows;
+    int64_t room, n;
+    int q;
+    __device__ void entry(const mt_dlog_entry &e) {
+        if (n < room && lane() == 0)
+            rows[n] = mt_delta_range{q, e.record, e.seq, e.kind, e.position, e.length, e.word, e.uid};
+        n++;
+    }
+};
+// Writes query q's words at out[off[q] ..) and, with row_off, its rows at rows[row_off[q] ..).
+// Words and rows are checked against the query's slots.  A span that is not well formed was
+// given no slot by the counting pass and is not walked again.
+__global__ void __launch_bounds__(MT_WAVE) k_dlog_gather(DevState st, int nq, const uint32_t *docs, const int32_t *from,
+                                                         const int64_t *off, const int64_t *row_off, int32_t *out,
+                                                         mt_delta_range *rows) {
+    const int q = blockIdx.x;
+    if (q >= nq) return;
+    const DlogSpan s = dlog_span(st, q, docs, from);
+    const int n = (int)min((int64_t)s.words, off[q + 1] - off[q]);
+    if (n <= 0) return;
+    int32_t *dst = out + off[q];
+    const uint32_t rel = (uint32_t)((uintptr_t)s.src - (uintptr_t)dst);
+    if ((rel & 15u) == 0u)
+        dlog_copy<4>(dst, s.src, n);
+    else if ((rel & 7u) == 0u)
+        dlog_copy<2>(dst, s.src, n);
+    else
+        for (int i = lane(); i < n; i += MT_WAVE) dst[i] = s.src[i];
+    if (!row_off) return;
+    DlogFill f{rows + row_off[q], row_off[q + 1] - row_off[q], 0, q};
+    if (f.room > 0) mt_dlog_walk(s.src, s.words, st.DLR != 0, f);
+}
+// mt_delta_log_reset for the listed documents
+__global__ void __launch_bounds__(MT_WAVE) k_dlog_reset_docs(DevState st, int n, const uint32_t *docs) {
+    const int i = blockIdx.x * MT_WAVE + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t doc = docs ? docs[i] : (uint32_t)i;
+    if (doc >= (uint32_t)st.n_docs) return;
+    st.hdr[doc].dlog_n = 0;
+    st.hdr[doc].pad[HDR_DLOG_OVF] = 0;
+}
+
 // ---------------------------------------------------------------- bulk segment read-outs
 // MergeTree.getContainingSegment / getPosition / getLength (MT/mergeTree.ts:1610-1667) for many
 // (doc, pos | uid, refSeq, client) queries: one wave per query over the document's rows in
@@ -1121,7 +1227,7 @@ __global__ void __launch_bounds__(MT_WAVE) k_regen(DevState st, int doc, mt_rege
 
 // Device time of a bulk read-out's kernels: up to two brackets of HIP events, created on first
 // use; `timed` counts the brackets of the last read-out whose kernels have finished
-// (read_timer: mt_last_text_ms, mt_last_props_ms, mt_last_locate).
+// (read_timer: mt_last_text_ms, mt_last_props_ms, mt_last_locate, mt_last_dlog_ms).
 struct ReadTimer {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     int timed = 0;
@@ -1151,7 +1257,9 @@ struct mt_handle {
     bool load_timed = false;   // ev_load / ev_load1 bracket the last snapshot load's kernels
     // mt_get_texts, mt_get_prop_runs_bulk: around the counting pass, around the gather; the bulk
     // segment read-outs: around their kernel
-    ReadTimer tm_txt, tm_prp, tm_loc;
+    ReadTimer tm_txt, tm_prp, tm_loc, tm_dlg;
+    uint32_t *d_rst = nullptr;   // mt_delta_log_reset_docs: the listed documents (rst_cap of them)
+    uint32_t rst_cap = 0;
     int64_t loc_n = 0, loc_host = 0;   // queries of the last segment read-out, of them answered by the host path
     // documents per workgroup of the LDS-tier replay (env MT_WPG=2 for two): measured on C2
     // the CU saturates at 16 resident documents (16 -> 18 per CU: 61.8 -> 64.6 ms)
@@ -1728,7 +1836,8 @@ void mt_destroy(mt_handle *h) {
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->ev_load) hipEventDestroy(h->ev_load);
     if (h->ev_load1) hipEventDestroy(h->ev_load1);
-    for (ReadTimer *t : {&h->tm_txt, &h->tm_prp, &h->tm_loc}) t->destroy();
+    for (ReadTimer *t : {&h->tm_txt, &h->tm_prp, &h->tm_loc, &h->tm_dlg}) t->destroy();
+    if (h->d_rst) hipFree(h->d_rst);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
 }
@@ -4104,6 +4213,140 @@ int mt_delta_log_reset(mt_handle *h) {
     hipLaunchKernelGGL(k_dlog_reset, dim3((h->n_docs + MT_WAVE - 1) / MT_WAVE), dim3(MT_WAVE), 0, h->stream, h->st);
     HIPCHK(h, hipGetLastError());
     return 0;
+}
+
+int mt_delta_log_reset_docs(mt_handle *h, uint32_t n, const uint32_t *docs) {
+    if (!h) return MT_E_INVALID;
+    const int bad = check_queries(h, "mt_delta_log_reset_docs", n, docs);
+    if (bad) return bad;
+    if (h->pending) SETTLE(h);
+    if (!h->st.DL || n == 0) return 0;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (docs) {   // the list lives in a buffer of the handle's: nothing to free behind the kernel
+        if (n > h->rst_cap) {
+            HIPCHK(h, hipStreamSynchronize(h->stream));   // (an earlier reset may still read the old one)
+            if (h->d_rst) HIPCHK(h, hipFree(h->d_rst));
+            h->d_rst = nullptr;
+            h->rst_cap = 0;
+            HIPCHK(h, hipMalloc((void **)&h->d_rst, (size_t)n * 4));
+            h->rst_cap = n;
+        }
+        HIPCHK(h, hipMemcpyAsync(h->d_rst, docs, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    hipLaunchKernelGGL(k_dlog_reset_docs, dim3((n + MT_WAVE - 1) / MT_WAVE), dim3(MT_WAVE), 0, h->stream, h->st, (int)n,
+                       docs ? h->d_rst : (const uint32_t *)nullptr);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// mt_get_delta_logs / mt_get_delta_logs_device: get_prop_runs_bulk's shape -- the counting pass
+// (words from the header, rows by the walk), one or two prefix sums, the gather.
+static int get_delta_logs(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *from_word, int64_t *off,
+                          int64_t *row_off, uint32_t *flags, void *out, uint64_t cap, void *rows, uint64_t cap_rows,
+                          bool device) {
+    if (!h || !off) return MT_E_INVALID;
+    int rc = check_queries(h, "mt_get_delta_logs", n, docs);
+    if (rc) return rc;
+    for (uint32_t q = 0; from_word && q < n; q++)
+        if (from_word[q] < 0) {
+            h->err = "mt_get_delta_logs: query " + std::to_string(q) + ": from_word " + std::to_string(from_word[q]);
+            return MT_E_INVALID;
+        }
+    HIPCHK(h, hipSetDevice(h->device));
+    SETTLE(h);
+    ReadTimer &tm = h->tm_dlg;
+    tm.timed = 0;
+    const int k = row_off ? 2 : 1;
+    int64_t *offs[2] = {off, row_off};
+    if (n == 0) {
+        for (int i = 0; i < k; i++)
+            if ((rc = empty_offsets(h, {offs[i]}, device))) return rc;
+        return 0;
+    }
+    if (!h->st.DL) {   // no log: zero words and rows, as mt_get_delta_log answers
+        for (int i = 0; i < k; i++)
+            if (device)
+                HIPCHK(h, hipMemset(offs[i], 0, ((size_t)n + 1) * 8));
+            else
+                memset(offs[i], 0, ((size_t)n + 1) * 8);
+        if (flags && device) HIPCHK(h, hipMemset(flags, 0, (size_t)n * 4));
+        if (flags && !device) memset(flags, 0, (size_t)n * 4);
+        return 0;
+    }
+    // extra: the word and row counts [n] each, the two offset arrays [n + 1] each, the flags [n]
+    const size_t words64 = (size_t)n * 4 + 2;
+    QueryCols qc;
+    HIPCHK(h, qc.upload(n, {docs, from_word}, words64 * 8 + (((size_t)n * 4 + 7) & ~(size_t)7)));
+    const uint32_t *d_docs = (const uint32_t *)qc.col[0];
+    const int32_t *d_from = (const int32_t *)qc.col[1];
+    int64_t *d_cnt[2] = {(int64_t *)qc.extra, (int64_t *)qc.extra + n};   // words, rows
+    int64_t *d_woff = device ? off : d_cnt[1] + n, *d_roff = device ? row_off : d_cnt[1] + 2 * (size_t)n + 1;
+    uint32_t *d_flags = (uint32_t *)((int64_t *)qc.extra + words64);
+    HIPCHK(h, tm.begin(0, h->stream));
+    hipLaunchKernelGGL(k_dlog_count, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_from, k == 2 ? 1 : 0,
+                       d_cnt[0], d_cnt[1], d_flags);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, tm.end(0, h->stream));
+    int64_t total[2] = {0, 0};
+    if ((rc = scan_counts(h, n, k, d_cnt, offs, device, total))) return rc;
+    tm.timed = 1;
+    // the flags: to the caller, and to the host when nobody else would see an overflow
+    std::vector<uint32_t> own_flags;
+    if (flags) HIPCHK(h, hipMemcpy(flags, d_flags, (size_t)n * 4, device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    if (!flags) {
+        own_flags.resize(n);
+        HIPCHK(h, hipMemcpy(own_flags.data(), d_flags, (size_t)n * 4, hipMemcpyDeviceToHost));
+    }
+    if (!rows) cap_rows = 0;
+    rc = after_counts(h, !out, cap >= (uint64_t)total[0] && (k == 1 || cap_rows >= (uint64_t)total[1]), total[0] == 0, [&] {
+        return "mt_get_delta_logs: the outputs hold " + std::to_string(cap) + " words and " + std::to_string(cap_rows) +
+               " rows, the results need " + std::to_string(total[0]) + " words and " + std::to_string(total[1]) + " rows";
+    });
+    if (rc < 0) return rc;
+    if (rc == RO_GATHER) {
+        if (!device) {
+            HIPCHK(h, hipMemcpy(d_woff, off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+            if (k == 2) HIPCHK(h, hipMemcpy(d_roff, row_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+        }
+        OutStage<int32_t> g_words;
+        OutStage<mt_delta_range> g_rows;
+        HIPCHK(h, g_words.open(out, device, (size_t)total[0]));
+        if (k == 2) HIPCHK(h, g_rows.open(rows, device, (size_t)total[1]));
+        HIPCHK(h, tm.begin(1, h->stream));
+        hipLaunchKernelGGL(k_dlog_gather, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_from, d_woff,
+                           k == 2 ? d_roff : (const int64_t *)nullptr, g_words.p, g_rows.p);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, tm.end(1, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        tm.timed = 2;
+        HIPCHK(h, g_words.copy_out(out, (size_t)total[0]));
+        if (k == 2) HIPCHK(h, g_rows.copy_out(rows, (size_t)total[1]));
+    }
+    for (uint32_t q = 0; q < (uint32_t)own_flags.size(); q++)
+        if (own_flags[q] & MT_DLOG_OVERFLOWED) {
+            h->err = "mt_get_delta_logs: query " + std::to_string(q) + ": document " + std::to_string(docs ? docs[q] : q) +
+                     " overflowed its delta log (delta_log_capacity) since its last reset";
+            return MT_E_OVERFLOW;
+        }
+    return 0;
+}
+
+int mt_get_delta_logs(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *from_word, int64_t *off,
+                      int64_t *row_off, uint32_t *flags, int32_t *out, uint64_t cap, mt_delta_range *rows,
+                      uint64_t cap_rows) {
+    return get_delta_logs(h, n, docs, from_word, off, row_off, flags, out, cap, rows, cap_rows, false);
+}
+
+int mt_get_delta_logs_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *from_word, void *off_dev,
+                             void *row_off_dev, void *flags_dev, void *out_dev, uint64_t cap, void *rows_dev,
+                             uint64_t cap_rows) {
+    return get_delta_logs(h, n, docs, from_word, (int64_t *)off_dev, (int64_t *)row_off_dev, (uint32_t *)flags_dev,
+                          out_dev, cap, rows_dev, cap_rows, true);
+}
+
+int mt_last_dlog_ms(mt_handle *h, float *out) {
+    if (!h || !out) return MT_E_INVALID;
+    return read_timer(h, h->tm_dlg, out);
 }
 
 // Debug: section timers of an MT_PROF build (s_memtime ticks [0, 64) and call / event counts

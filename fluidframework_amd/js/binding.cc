@@ -734,6 +734,101 @@ napi_value DeltaLogReset(napi_env env, napi_callback_info info) {
     return nullptr;
 }
 
+// getDeltaLogs(h, docs|null, fromWord|null[, ranges]) -> {off: Float64Array [n + 1], words:
+// Int32Array, flags: Uint32Array [n]} and, with ranges, {rowOff: Float64Array [n + 1], rows:
+// Int32Array, 8 words per row: the mt_delta_range records}   (mt_get_delta_logs: getDeltaLog from
+// word fromWord[q] on for many documents in one counting pass and one gather.  An overflowed
+// document does not throw: flags[q] & 1.)
+napi_value GetDeltaLogs(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    size_t argc = 4;
+    if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 3) {
+        napi_throw_type_error(env, nullptr, "wrong number of arguments");
+        return nullptr;
+    }
+    Handle *hd = get_handle(env, argv[0]);
+    if (!hd) return nullptr;
+    bool ranges = false;
+    if (argc >= 4) NAPI_CALL(env, napi_coerce_to_bool(env, argv[3], &argv[3]));
+    if (argc >= 4) NAPI_CALL(env, napi_get_value_bool(env, argv[3], &ranges));
+    void *ptrs[2] = {nullptr, nullptr};
+    size_t lens[2] = {0, 0};
+    const napi_typedarray_type want[2] = {napi_uint32_array, napi_int32_array};
+    for (int i = 0; i < 2; i++) {
+        napi_valuetype vt;
+        NAPI_CALL(env, napi_typeof(env, argv[1 + i], &vt));
+        if (vt == napi_null || vt == napi_undefined) continue;
+        napi_typedarray_type t;
+        napi_value ab;
+        size_t off;
+        if (napi_get_typedarray_info(env, argv[1 + i], &t, &lens[i], &ptrs[i], &ab, &off) != napi_ok || t != want[i]) {
+            napi_throw_type_error(env, nullptr, "getDeltaLogs: docs is a Uint32Array, fromWord an Int32Array (or null)");
+            return nullptr;
+        }
+        if (!ptrs[i]) ptrs[i] = &lens[i];   // (an empty array: any non-null pointer, never read)
+    }
+    const size_t n = ptrs[0] ? lens[0] : mt_num_docs(hd->h);
+    if (ptrs[1] && lens[1] != n) {
+        napi_throw_range_error(env, nullptr, "getDeltaLogs: fromWord holds one entry per query");
+        return nullptr;
+    }
+    const uint32_t *docs = (const uint32_t *)ptrs[0];
+    const int32_t *from = (const int32_t *)ptrs[1];
+    std::vector<int64_t> off(n + 1), roff(n + 1);
+    void *fd;
+    napi_value fab;
+    NAPI_CALL(env, napi_create_arraybuffer(env, std::max<size_t>(n, 1) * 4, &fd, &fab));
+    int rc = mt_get_delta_logs(hd->h, (uint32_t)n, docs, from, off.data(), ranges ? roff.data() : nullptr, (uint32_t *)fd,
+                               nullptr, 0, nullptr, 0);
+    if (rc) return throw_rc(env, hd, rc, "mt_get_delta_logs");
+    const size_t nw = (size_t)off[n], nr = ranges ? (size_t)roff[n] : 0;
+    void *wd, *rd;
+    napi_value wab, rab, obj, v;
+    NAPI_CALL(env, napi_create_arraybuffer(env, std::max<size_t>(nw, 1) * 4, &wd, &wab));
+    NAPI_CALL(env, napi_create_arraybuffer(env, std::max<size_t>(nr, 1) * sizeof(mt_delta_range), &rd, &rab));
+    rc = mt_get_delta_logs(hd->h, (uint32_t)n, docs, from, off.data(), ranges ? roff.data() : nullptr, (uint32_t *)fd,
+                           (int32_t *)wd, nw, (mt_delta_range *)rd, nr);
+    if (rc) return throw_rc(env, hd, rc, "mt_get_delta_logs");
+    NAPI_CALL(env, napi_create_object(env, &obj));
+    for (int i = 0; i < (ranges ? 2 : 1); i++) {
+        void *od;
+        napi_value oab;
+        NAPI_CALL(env, napi_create_arraybuffer(env, (n + 1) * 8, &od, &oab));
+        for (size_t q = 0; q <= n; q++) ((double *)od)[q] = (double)(i ? roff[q] : off[q]);
+        NAPI_CALL(env, napi_create_typedarray(env, napi_float64_array, n + 1, oab, 0, &v));
+        NAPI_CALL(env, napi_set_named_property(env, obj, i ? "rowOff" : "off", v));
+    }
+    NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, nw, wab, 0, &v));
+    NAPI_CALL(env, napi_set_named_property(env, obj, "words", v));
+    NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, n, fab, 0, &v));
+    NAPI_CALL(env, napi_set_named_property(env, obj, "flags", v));
+    if (ranges) {
+        NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, nr * (sizeof(mt_delta_range) / 4), rab, 0, &v));
+        NAPI_CALL(env, napi_set_named_property(env, obj, "rows", v));
+    }
+    return obj;
+}
+
+// deltaLogResetDocs(h, docs) -- empties the listed documents' delta logs (mt_delta_log_reset_docs)
+napi_value DeltaLogResetDocs(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    Handle *hd = get_handle(env, argv[0]);
+    if (!hd) return nullptr;
+    napi_typedarray_type t;
+    napi_value ab;
+    size_t off, len = 0;
+    void *p = nullptr;
+    if (napi_get_typedarray_info(env, argv[1], &t, &len, &p, &ab, &off) != napi_ok || t != napi_uint32_array) {
+        napi_throw_type_error(env, nullptr, "deltaLogResetDocs: docs is a Uint32Array");
+        return nullptr;
+    }
+    if (len == 0) return nullptr;
+    const int rc = mt_delta_log_reset_docs(hd->h, (uint32_t)len, (const uint32_t *)p);
+    if (rc) return throw_rc(env, hd, rc, "mt_delta_log_reset_docs");
+    return nullptr;
+}
+
 // maintenanceCounts(h) -> Uint32Array [nDocs * 3]: SPLIT, APPEND, UNLINK per document
 // (mergeTreeMaintenanceCallback events; only with deltaLogCapacity > 0)
 napi_value MaintenanceCounts(napi_env env, napi_callback_info info) {
@@ -951,7 +1046,8 @@ napi_value Init(napi_env env, napi_value exports) {
                  {"startCollaboration", StartCollaboration},
                {"applyOps", ApplyOps},     {"loadSnapshots", LoadSnapshots},     {"status", Status},             {"getLength", GetLength},
                {"getText", GetText},       {"getTexts", GetTexts},         {"getPropRuns", GetPropRuns}, {"getPropRunsBulk", GetPropRunsBulk},   {"getDeltaLog", GetDeltaLog},
-               {"deltaLogReset", DeltaLogReset},
+               {"deltaLogReset", DeltaLogReset},       {"getDeltaLogs", GetDeltaLogs},
+               {"deltaLogResetDocs", DeltaLogResetDocs},
                {"maintenanceCounts", MaintenanceCounts},
                {"checksums", Checksums},   {"lastKernelMs", LastKernelMs}, {"numDocs", NumDocs},
                {"regeneratePending", RegeneratePending}, {"decodeSummaries", DecodeSummaries},

@@ -122,6 +122,10 @@ class GpuMergeTreeBatch {
         this.views = new Map();
         this.logPos = new Int32Array(nDocs);
         this.wantsDeltas = !!options.deltaLogCapacity;
+        // deltaRanges: every flush also keeps one row per delta segment of every document
+        // (getDeltaRanges), taken on the device with the drain
+        this.wantsRanges = this.wantsDeltas && !!options.deltaRanges;
+        this.lastRanges = null;
         this.segObjs = Array.from({ length: nDocs }, () => new Map());   // per document: id -> segment
         this.inflight = null;
     }
@@ -230,12 +234,42 @@ class GpuMergeTreeBatch {
             // every view drains its records, then the device logs restart empty: a long-lived
             // batch never runs out of log capacity (a single flush that overflows it throws)
             try {
-                for (const v of this.views.values()) { v._emitDeltas(); }
+                // one drain (mt_get_delta_logs) for all the documents that have views, from each
+                // one's logPos; every view then replays its slice
+                const views = [...this.views.values()];
+                const docs = this.wantsRanges ? null : Uint32Array.from(views, (v) => v.doc);
+                this.lastRanges = null;
+                if (views.length > 0 || this.wantsRanges) {
+                    const from = docs === null ? this.logPos : Int32Array.from(views, (v) => this.logPos[v.doc]);
+                    const r = native.getDeltaLogs(this.h, docs, from, this.wantsRanges);
+                    if (this.wantsRanges) { this.lastRanges = { rowOff: r.rowOff, rows: r.rows, flags: r.flags }; }
+                    views.forEach((v, k) => {
+                        const q = docs === null ? v.doc : k;
+                        if (r.flags[q] & 1) {
+                            throw new Error(`mt_get_delta_logs failed (-5): document ${v.doc} overflowed its delta log ` +
+                                "(delta_log_capacity) since the last mt_delta_log_reset");
+                        }
+                        v._emitDeltas(r.words.subarray(r.off[q], r.off[q + 1]), from[q]);
+                    });
+                }
             } finally {
                 native.deltaLogReset(this.h);
                 this.logPos.fill(0);
             }
         }
+    }
+
+    /**
+     * The delta segments of the last flush (batches created with deltaRanges: 1): {rowOff:
+     * Float64Array [nDocs + 1], rows: Int32Array, flags: Uint32Array [nDocs]} -- document d's rows
+     * are rows[8 * rowOff[d] .. 8 * rowOff[d + 1]), eight words each (query = d, record, seq,
+     * operation, position, length, word, uid: mt_delta_range), what SequenceDeltaEvent.ranges is
+     * made of, read on the device without parsing the log.  null before the first flush.
+     */
+    getDeltaRanges() {
+        this.flush();
+        if (!this.wantsRanges) { throw new Error("getDeltaRanges: the batch was not created with deltaRanges"); }
+        return this.lastRanges;
     }
 
     status() { this.flush(); return native.status(this.h); }
@@ -828,7 +862,7 @@ class GpuClient {
     }
 
     /**
-     * Replays the device delta log of the last flush into the reference's callbacks:
+     * Replays the document's slice of the last flush's drain into the reference's callbacks:
      * mergeTreeDeltaCallback(opArgs, {operation, deltaSegments}) (mergeTreeDeltaCallback.ts:
      * 33-59; call sites mergeTree.ts:2014-2021, 2625-2632, 2738-2745) with opArgs {op,
      * sequencedMessage, groupOp} and deltaSegments [{segment, propertyDeltas}] -- segment =
@@ -837,14 +871,13 @@ class GpuClient {
      * mergeTreeMaintenanceCallback({operation: SPLIT -2 | APPEND -1 | UNLINK -3,
      * deltaSegments}) (mergeTree.ts:1343-1373, 2264-2269), in the reference's order.
      */
-    _emitDeltas() {
+    _emitDeltas(log, base) {
         const cb = this.mergeTreeDeltaCallback, mcb = this.mergeTreeMaintenanceCallback;
         const rich = this.batch.rich;
-        const log = native.getDeltaLog(this.batch.h, this.doc);
         const msgs = (this.batch.applied && this.batch.applied[this.doc]) || [];
         const objs = this.batch.segObjs[this.doc];
         let mi = 0, member = 0, lastSeq = null;
-        let i = this.batch.logPos[this.doc];
+        let i = 0;   // (log: the document's words from `base` on)
         while (i + 3 <= log.length) {
             const seq = log[i], kind = log[i + 1], n = log[i + 2];
             i += 3;
@@ -915,7 +948,7 @@ class GpuClient {
                 this._evPos = undefined;
             }
         }
-        this.batch.logPos[this.doc] = i;
+        this.batch.logPos[this.doc] = base + i;
     }
 }
 

@@ -528,6 +528,61 @@ int mt_get_delta_log(mt_handle *h, uint32_t doc, int32_t *out, uint32_t cap, uin
 /* Empties every document's delta log and clears its overflow flag (asynchronous, on the
    handle's stream): a reader that has consumed the records calls it before the next batch. */
 int mt_delta_log_reset(mt_handle *h);
+/* The delta logs of n queries (doc, from_word) in one counting pass and one gather on the
+   device, and optionally the (seq, kind, position, length) of every delta segment in them --
+   what SequenceDeltaEvent.ranges is made of -- without parsing the records on the host.
+   Queries, arguments and errors are mt_get_texts': docs NULL: documents 0..n-1 (n <= n_docs);
+   the same document may appear in many queries, in any order; a doc >= n_docs or a
+   from_word[q] < 0 is MT_E_INVALID, checked before anything is written (mt_last_error names the
+   query); the call settles the handle first.  from_word NULL: 0 for every query.
+   - Query q's words are the document's log from word from_word[q] to its end,
+     dlog[from_word[q] .. min(max(dlog_n, 0), delta_log_capacity)), at out + off[q].  A reader
+     that keeps each document's word count reads only what a later batch appended.
+     from_word[q] equal to the word count gives an empty result; beyond it an empty result and
+     MT_DLOG_PAST in flags[q].
+   - off[n + 1] always receives the prefix sums of the word counts.  out NULL: sizing only (rows
+     is then ignored).  cap < off[n] or cap_rows < row_off[n]: MT_E_OVERFLOW, nothing written to
+     out or rows; mt_last_error names both needs.
+   - row_off NULL: no rows (the records are not walked).  Otherwise row_off[n + 1] receives the
+     prefix sums of the row counts and query q's rows are rows[row_off[q] .. row_off[q + 1]):
+     one mt_delta_range per entry of every record of the query's words, in log order, on plain
+     and rich logs (delta_log_mode 1, where the maintenance records are rows too: kind < 0).
+     from_word[q] must be a record boundary: words that are not a whole number of well-formed
+     records give the query zero rows and MT_DLOG_BAD (its words are delivered all the same).
+   - A document that overflowed its log does not fail the call: the records it kept are
+     delivered and flags[q] carries MT_DLOG_OVERFLOWED.  With flags NULL such a query makes the
+     call return MT_E_OVERFLOW after everything is filled (mt_last_error names the first one).
+   - A handle without a log (delta_log_capacity 0) answers zero words and rows for every query. */
+#define MT_DLOG_OVERFLOWED 1u  /* the document dropped records since its last reset */
+#define MT_DLOG_PAST       2u  /* from_word > the document's word count: nothing returned */
+#define MT_DLOG_BAD        4u  /* the walk left the span: from_word was not a record boundary */
+typedef struct mt_delta_range {   /* 32 bytes, one per delta segment */
+    int32_t query;     /* q */
+    int32_t record;    /* index of its record within the query's words (records with n == 0 count) */
+    int32_t seq, kind; /* the record's header */
+    int32_t position;  /* kind >= 0: the entry's position; maintenance entry: the ext position, else -1 */
+    int32_t length;    /* cachedLength */
+    int32_t word;      /* offset of the entry's first word, relative to the query's first word */
+    uint32_t uid;      /* the ext uid (entry flags & 4), else 0xFFFFFFFF */
+} mt_delta_range;
+int mt_get_delta_logs(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *from_word,
+                      int64_t *off /* [n+1] */, int64_t *row_off /* [n+1] or NULL */, uint32_t *flags /* [n] or NULL */,
+                      int32_t *out, uint64_t cap, mt_delta_range *rows, uint64_t cap_rows);
+/* The same with off, row_off (int64[n + 1]), flags (uint32[n]), out (int32[cap]) and rows
+   (mt_delta_range[cap_rows]) in device memory on the handle's device; docs / from_word stay
+   host arrays.  The prefix sums are taken on the device; the call returns once the results are
+   written. */
+int mt_get_delta_logs_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *from_word,
+                             void *off_dev, void *row_off_dev, void *flags_dev, void *out_dev, uint64_t cap,
+                             void *rows_dev, uint64_t cap_rows);
+/* mt_delta_log_reset for the n listed documents only (asynchronous, on the handle's stream): a
+   reader that follows some of the documents consumes their logs and leaves the others'.
+   Duplicates are harmless; a doc >= n_docs is MT_E_INVALID (nothing is reset). */
+int mt_delta_log_reset_docs(mt_handle *h, uint32_t n, const uint32_t *docs);
+/* Device time of the most recent mt_get_delta_logs(_device) call's two kernels (HIP events):
+   out[0] the counting pass (with the walk when rows are asked for), out[1] the gather (0 after
+   a sizing call). */
+int mt_last_dlog_ms(mt_handle *h, float *out /* [2]: counting pass (with the walk), gather */);
 
 /* mergeTreeMaintenanceCallback events per document since its creation (only with
    delta_log_capacity > 0, MT_E_INVALID otherwise): out[3*doc + {0,1,2}] = SPLIT

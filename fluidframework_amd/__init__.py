@@ -754,6 +754,112 @@ class MergeTreeBatch:
         self._check(self.lib.mt_last_locate(self.h, _native.ptr(out), ctypes.byref(ms)), "mt_last_locate")
         return int(out[0]), int(out[1]), float(ms.value)
 
+    # bulk marker queries (mt_find_tiles / mt_find_markers_by_id): SharedString.findTile and
+    # getMarkerFromId for many queries in one launch, in the replica's own view
+    TILE_LABELS_KEY, MARKER_ID_KEY = "referenceTileLabels", "markerId"
+
+    def _label_ids(self, interner, label):
+        """Ids (ascending, without flag bits) of the interned values that yield `label` when
+        JavaScript iterates them: lists holding it, strings holding it as a character.  Kept per
+        label and extended when the interner has grown."""
+        cache = getattr(self, "_tile_labels", None)
+        if cache is None or cache[0] is not interner:
+            cache = self._tile_labels = (interner, {})
+        seen, ids = cache[1].setdefault(label, [0, []])
+        vals = interner.vals
+        for i in range(seen, len(vals)):
+            v = vals[i]
+            if (isinstance(v, list) and any(isinstance(x, str) and x == label for x in v)) or \
+                    (isinstance(v, str) and len(label) == 1 and label in v):
+                ids.append(i)
+        cache[1][label][0] = len(vals)
+        return ids
+
+    def _tile_queries(self, docs, pos, labels, preceding, interner):
+        if interner is None:
+            raise ValueError("find_tiles: pass the interner the batches were encoded with")
+        if docs is not None:
+            docs = np.ascontiguousarray(docs, dtype=np.uint32).reshape(-1)
+        n = len(docs) if docs is not None else self.n_docs
+        if pos is None or np.isscalar(pos):
+            pos = np.full(n, -1 if pos is None else int(pos), dtype=np.int32)
+        elif isinstance(pos, np.ndarray) and pos.dtype.kind in "iu":
+            pos = np.ascontiguousarray(pos, dtype=np.int32).reshape(-1)
+        else:
+            pos = np.ascontiguousarray([-1 if p is None else int(p) for p in pos], dtype=np.int32)
+        if len(pos) != n:
+            raise ValueError("find_tiles: one position per query")
+        one = isinstance(labels, str)
+        names = [labels] if one else sorted(set(labels))
+        if not one and len(labels) != n:
+            raise ValueError("find_tiles: one label per query")
+        index = {s: i for i, s in enumerate(names)}
+        sets = [self._label_ids(interner, s) for s in names]
+        off = np.zeros(len(names) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(s) for s in sets])
+        vals = np.ascontiguousarray([i for s in sets for i in s], dtype=np.uint32)
+        label = np.zeros(n, dtype=np.uint32) if one else np.ascontiguousarray([index[s] for s in labels], dtype=np.uint32)
+        prec = np.ascontiguousarray(np.broadcast_to(np.asarray(preceding, dtype=bool), (n,)), dtype=np.uint8)
+        # a key the interner has never seen is held by no record
+        key = 0xFFFFFFFF if interner.synthetic else interner.key_ids.get(self.TILE_LABELS_KEY, 0xFFFFFFFF)
+        return n, docs, pos, prec, label, key, len(names), off, vals
+
+    def find_tiles(self, docs, pos, labels, preceding=True, interner=None):
+        """SharedString.findTile(pos, label, preceding) for each (doc, pos, label, preceding):
+        mt_seg_hit records (_native.SEG_HIT_DTYPE) of the nearest tile marker carrying the label
+        at or before (preceding) / at or after the position; row -1: none; `position` is the
+        marker's.  pos entries may be None (undefined); labels: one string, or one per query;
+        preceding: one flag, or one per query."""
+        n, docs, pos, prec, label, key, nl, off, vals = self._tile_queries(docs, pos, labels, preceding, interner)
+        out = np.zeros(n, dtype=_native.SEG_HIT_DTYPE)
+        self._check(self.lib.mt_find_tiles(self.h, n, _native.ptr(docs), _native.ptr(pos), _native.ptr(prec),
+                                           _native.ptr(label), key, nl, _native.ptr(off), _native.ptr(vals),
+                                           _native.ptr(out)), "mt_find_tiles")
+        return out
+
+    def find_tiles_device(self, docs, pos, labels, preceding=True, interner=None):
+        """find_tiles with the records left on the handle's device: an int32 torch tensor [n, 12]
+        (as locate_segments_device)."""
+        import torch
+        n, docs, pos, prec, label, key, nl, off, vals = self._tile_queries(docs, pos, labels, preceding, interner)
+        out = torch.empty((n, _native.SEG_HIT_DTYPE.itemsize // 4), dtype=torch.int32,
+                          device=torch.device("cuda", self.device))
+        self._check(self.lib.mt_find_tiles_device(self.h, n, _native.ptr(docs), _native.ptr(pos), _native.ptr(prec),
+                                                  _native.ptr(label), key, nl, _native.ptr(off), _native.ptr(vals),
+                                                  ctypes.c_void_p(out.data_ptr())), "mt_find_tiles_device")
+        return out
+
+    def find_markers_by_id(self, docs, ids, interner=None):
+        """SharedString.getMarkerFromId(id) for each (doc, id): the marker row, removed or not,
+        whose markerId property is the id (row -1: none in the tree; flags MT_MARK_DUP: several
+        rows carry it, the first one answers).  An id the interner has never seen is in no
+        document."""
+        if interner is None:
+            raise ValueError("find_markers_by_id: pass the interner the batches were encoded with")
+        if docs is not None:
+            docs = np.ascontiguousarray(docs, dtype=np.uint32).reshape(-1)
+        n = len(docs) if docs is not None else self.n_docs
+        ids = [ids] * n if isinstance(ids, str) else list(ids)
+        if len(ids) != n:
+            raise ValueError("find_markers_by_id: one id per query")
+        from .wire import canonical_json
+        none = 0xFFFFFFFF
+        known = {} if interner.synthetic else interner.val_ids
+        # (a falsy id is never mapped: MT/mergeTree.ts:281, :2109)
+        val = np.ascontiguousarray([known.get(canonical_json(i), none) if i else none for i in ids], dtype=np.uint32)
+        key = none if interner.synthetic else interner.key_ids.get(self.MARKER_ID_KEY, none)
+        out = np.zeros(n, dtype=_native.SEG_HIT_DTYPE)
+        self._check(self.lib.mt_find_markers_by_id(self.h, n, _native.ptr(docs), key, _native.ptr(val),
+                                                   _native.ptr(out)), "mt_find_markers_by_id")
+        return out
+
+    def last_tiles(self):
+        """(queries, rows examined, kernel ms) of the last bulk marker query."""
+        out = np.zeros(2, dtype=np.int64)
+        ms = ctypes.c_float()
+        self._check(self.lib.mt_last_tiles(self.h, _native.ptr(out), ctypes.byref(ms)), "mt_last_tiles")
+        return int(out[0]), int(out[1]), float(ms.value)
+
     def get_prop_runs(self, doc):
         nr, nw = ctypes.c_uint32(), ctypes.c_uint32()
         self._check(self.lib.mt_get_prop_runs(self.h, doc, None, 0, ctypes.byref(nr), None, 0,

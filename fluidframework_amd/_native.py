@@ -50,6 +50,7 @@ SEG_HIT_DTYPE = np.dtype([("row", "<i4"), ("uid", "<u4"), ("position", "<i4"), (
                           ("removed_seq", "<i4"), ("removed_client", "<i4"), ("marker_ref_type", "<i4"),
                           ("flags", "<u4")])
 MT_HIT_HOST = 1
+MT_MARK_DUP = 2   # bulk marker queries: more than one marker row carries the id
 
 # mt_delta_range (include/mt_replay.h): one delta segment of mt_get_delta_logs' rows
 DELTA_RANGE_DTYPE = np.dtype([("query", "<i4"), ("record", "<i4"), ("seq", "<i4"), ("kind", "<i4"),
@@ -165,6 +166,11 @@ SIGNATURES = [
     ("mt_get_view_lengths_bulk", _I, [_P, _U32, _P, _P, _P, _P]),
     ("mt_resolve_remote_positions", _I, [_P, _U32, _P, _P, _P, _P, _P]),
     ("mt_last_locate", _I, [_P, _P, _P]),
+    ("mt_find_tiles", _I, [_P, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _P]),
+    ("mt_find_tiles_device", _I, [_P, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _P]),
+    ("mt_find_markers_by_id", _I, [_P, _U32, _P, _U32, _P, _P]),
+    ("mt_find_markers_by_id_device", _I, [_P, _U32, _P, _U32, _P, _P]),
+    ("mt_last_tiles", _I, [_P, _P, _P]),
 ]
 
 _lib = None

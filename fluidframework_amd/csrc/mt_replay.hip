@@ -1087,6 +1087,277 @@ __global__ void __launch_bounds__(MT_WAVE) k_locate(DevState st, int nq, const u
     }
 }
 
+// ---------------------------------------------------------------- bulk marker queries
+// MergeTree.findTile (MT/mergeTree.ts:1796-1822) and getMarkerFromId (:1965) for many queries in
+// the observer view: one wave per query, one lane per row in chunks of 64.
+// A row qualifies for a label when it is a marker with the Tile bit whose property record holds
+// the tile key with a value of the label's set (refHasTileLabel, :620-635); by id, when it is a
+// marker whose record holds the id key with the id's value.  With H the first row whose
+// inclusive observer prefix exceeds pos:
+//   preceding (search + tileShift, :1030-1069, :1830-1862): the last qualifying visible row at or
+//     before H; no H (pos >= length, or pos < 0: undefined): the last one of the document;
+//   following (backwardSearch, :1864-1907): the first qualifying visible row at or after H;
+//     pos < 0: the first one of the document; pos == length: the last row, removed or not, when
+//     it qualifies; pos > length: nothing.
+// Interior blocks answer from rightmostTiles / leftmostTiles, which hold rows of positive
+// localNetLength only (:262-317): hence "visible".
+struct TileQuery {         // wave-uniform
+    uint32_t key;          // the tile key (mode 0) / the id key (mode 1)
+    const uint32_t *vals;  // mode 0: the label's value ids, ascending
+    int nvals;
+    uint32_t id;           // mode 1: the id's value id
+    const uint32_t *pr;    // the document's property records
+    uint32_t P;
+};
+struct TileWalk {          // wave-uniform
+    int opos, rows;        // observer length and rows before the current chunk
+    int examined;          // rows tested
+    bool hfound, found, dup;
+    mt_seg_hit hit;
+};
+// the row test of one lane: its row (a, b) is a valid one of the chunk
+template <int kMode> __device__ __forceinline__ bool tile_row_test(const TileQuery &Q, bool v, v4u b) {
+    const bool mk = v & ((b.z & MT_MARKER_BIT) != 0u);
+    // a handle outside the arena or a count over MT_KMAX reads as no record; the words are
+    // loaded unconditionally (record 0 for the other lanes) and masked
+    const uint32_t hi = (mk & (b.y < Q.P)) ? b.y : 0u;
+    const uint32_t *rec = Q.pr + (size_t)hi * MT_PREC;
+    const uint32_t c = rec[0];
+    const bool ok = (hi != 0u) & (c <= (uint32_t)MT_KMAX);
+    uint32_t tv = MT_VAL_NULL;   // the key's value (one pair per key)
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)MT_KMAX; k++) {
+        const uint32_t kk = rec[1 + 2 * k], vv = rec[2 + 2 * k];
+        tv = ((k < c) & (kk == Q.key)) ? vv : tv;
+    }
+    const bool has = ok & (tv < MT_VAL_UNDEF);
+    const uint32_t mv = tv & ~(MT_VAL_FALSY_BIT | MT_VAL_NOMATCH_BIT);
+    if (kMode == 1) return has & (mv == Q.id);
+    bool in = false;
+    for (int j = 0; j < Q.nvals; j++) in = in | (Q.vals[j] == mv);   // (a handful of ids; the span is wave-uniform)
+    return has & in & ((b.x & 1u) != 0u);
+}
+__device__ __forceinline__ void tile_fill(TileWalk &W, int l, int base, v4i a, v4u b, int excl) {
+    const int x = bcast(a.x, l), y = bcast(a.y, l), z = bcast(a.z, l), w = bcast(a.w, l);
+    const uint32_t bx = (uint32_t)bcast((int)b.x, l), bz = (uint32_t)bcast((int)b.z, l);
+    W.found = true;
+    W.hit.row = W.rows + base + l;
+    W.hit.uid = bz & ~MT_MARKER_BIT;
+    W.hit.position = W.hit.local_position = W.opos + bcast(excl, l);
+    W.hit.offset = 0;
+    W.hit.length = x;
+    W.hit.seq = y >= MT_LOCAL_BASE ? -1 : y;
+    W.hit.client = (int)(short)(w & 0xFFFF);
+    W.hit.removed_seq = z >= MT_LOCAL_BASE ? -1 : z;
+    W.hit.removed_client = z == MT_RSEQ_NONE ? MT_RSEQ_NONE : (int)(short)((uint32_t)w >> 16);
+    W.hit.marker_ref_type = (bz & MT_MARKER_BIT) ? (int32_t)bx : -1;
+}
+// rows [base, base + 64) of a range of n rows.  kMode 0: until H is known (W.hfound) the chunk
+// is searched for it; preceding takes the highest qualifying visible lane at or below H (any
+// lane while there is no H), following the lowest one at or above H (none before H).  kMode 1:
+// the first matching lane, then any further match marks a duplicate.  last: the pos == length
+// edge -- lane n - 1 - base answers if it qualifies, whatever its length.
+template <int kMode>
+__device__ __forceinline__ void tile_chunk(TileWalk &W, const TileQuery &Q, const v4i *A, const v4u *Bv, int base, int n,
+                                           int pos, bool prec, bool last) {
+    const int i = base + lane();
+    const bool v = i < n;
+    const int ic = v ? i : 0;
+    v4i a = A[ic];   // (unconditional: DESIGN section 10)
+    v4u b = Bv[ic];
+    if (!v) {
+        a = v4i{0, 0, MT_RSEQ_NONE, 0};
+        b = v4u{0u, 0u, 0u, 0u};
+    }
+    const int ol = obs_len(a);
+    const int oin = wave_scan_incl(ol);
+    const bool q = tile_row_test<kMode>(Q, v, b);
+    W.examined += min(n - base, MT_WAVE);
+    if (kMode == 1) {
+        const u64 m = ballot(q);
+        if (m) {
+            W.dup = W.dup | W.found | ((m & (m - 1)) != 0ull);
+            if (!W.found) tile_fill(W, first_lane(m), base, a, b, oin - ol);
+        }
+    } else if (last) {
+        const int l = n - 1 - base;
+        if ((ballot(q) >> l) & 1ull) tile_fill(W, l, base, a, b, oin - ol);
+    } else {
+        u64 lanes = ~0ull;
+        if (!W.hfound && pos >= 0) {
+            const u64 mh = ballot(v & (W.opos + oin > pos));
+            if (mh) {
+                const int lh = first_lane(mh);
+                W.hfound = true;
+                lanes = prec ? (~0ull >> (63 - lh)) : (~0ull << lh);
+            } else if (!prec) {
+                lanes = 0ull;
+            }
+        }
+        const u64 cand = ballot(q & (ol > 0)) & lanes;
+        if (cand) tile_fill(W, prec ? 63 - __clzll((long long)cand) : first_lane(cand), base, a, b, oin - ol);
+    }
+    W.opos += bcast(oin, 63);
+}
+template <int kMode>
+__global__ void __launch_bounds__(MT_WAVE) k_tiles(DevState st, int nq, const uint32_t *docs, const int32_t *posv,
+                                                   const uint32_t *sel, uint32_t key, const uint32_t *label_off,
+                                                   const uint32_t *label_vals, int skip, mt_seg_hit *out,
+                                                   int32_t *examined) {
+    const int q = blockIdx.x;
+    if (q >= nq) return;
+    const int doc = docs ? (int)docs[q] : q;
+    // mode 0: sel = label index | preceding << 31; mode 1: sel = the id's value id
+    const uint32_t s = sel[q];
+    const int pos = kMode == 0 ? posv[q] : -1;
+    const bool prec = kMode == 0 && (s >> 31) != 0u;
+    TileWalk W;
+    memset(&W.hit, 0, sizeof(W.hit));
+    W.hit.row = -1;
+    W.opos = W.rows = W.examined = 0;
+    W.hfound = W.found = W.dup = false;
+    if (doc >= 0 && doc < st.n_docs) {   // (the host refuses the others)
+        const DocHdr h = st.hdr[doc];
+        const SegRanges R = seg_ranges(st, doc, h);
+        const PagedBase ar = doc_paged(st, doc);   // (the arenas of the document's region)
+        TileQuery Q;
+        Q.key = key;
+        Q.P = (uint32_t)ar.P;
+        Q.pr = ar.props + (size_t)h.props_half * ar.P * MT_PREC;
+        Q.id = s;
+        Q.vals = label_vals;
+        Q.nvals = 0;
+        if (kMode == 0) {
+            const uint32_t l = s & 0x7FFFFFFFu, lo = label_off[l];
+            Q.vals = label_vals + lo;
+            Q.nvals = (int)(label_off[l + 1] - lo);
+        }
+        bool walk = true;
+        int total = -1;   // the observer length, once the directory has given it
+        if (kMode == 0 && R.paged && skip && R.nr > 0) {
+            const int PP = ar.PP;
+            auto page_of = [&](int j) {   // (a directory entry outside the region reads as page 0)
+                const int pg = R.dir[j];
+                return pg < PP ? pg : 0;
+            };
+            // H's page by the directory's observer lengths, 64 positions at a time; following
+            // with pos undefined starts at the first page and needs no scan
+            int hp = -1, nrows = 0;
+            if (prec || pos >= 0) {
+                for (int base = 0; hp < 0 && base < R.nr; base += MT_WAVE) {
+                    const int j = base + lane();
+                    const bool v = j < R.nr;
+                    const PageMeta pm = R.meta[page_of(v ? j : 0)];
+                    const int ob = v ? pm.obs : 0, ns = v ? min((int)pm.nseg, MT_PG_SLOTS) : 0;
+                    const int oin = wave_scan_incl(ob), nin = wave_scan_incl(ns);
+                    const u64 m = pos >= 0 ? ballot(v & (W.opos + oin > pos)) : 0ull;
+                    if (m) {
+                        const int l = first_lane(m);
+                        hp = base + l;
+                        W.opos += bcast(oin - ob, l);
+                        nrows += bcast(nin - ns, l);
+                    } else {
+                        W.opos += bcast(oin, 63);
+                        nrows += bcast(nin, 63);
+                    }
+                }
+            } else {
+                hp = 0;
+                W.hfound = true;   // every row of the document is at or after H
+            }
+            walk = false;
+            if (hp < 0) {   // no H: W.opos is the document's length, nrows its rows
+                total = W.opos;
+                const PageMeta pm = R.meta[page_of(R.nr - 1)];
+                const int ns = min((int)pm.nseg, MT_PG_SLOTS);
+                const size_t p0 = (size_t)page_of(R.nr - 1) * MT_PG_SLOTS;
+                W.opos -= pm.obs;
+                W.rows = nrows - ns;
+                if (prec) {
+                    hp = R.nr - 1;   // the last qualifying visible row of the document: from the end
+                } else if (pos == total && ns > 0) {
+                    tile_chunk<kMode>(W, Q, R.A + p0, R.B + p0, 0, ns, pos, prec, true);
+                }
+            } else {
+                W.rows = nrows;
+            }
+            // H's page (or the end the walk starts from), then away from it one page at a time
+            const bool had_h = hp >= 0 && total < 0 && pos >= 0;
+            for (int j = hp; hp >= 0 && j >= 0 && j < R.nr && !W.found; j += prec ? -1 : 1) {
+                const int pg = page_of(j);
+                const PageMeta pm = R.meta[pg];
+                const int ns = min((int)pm.nseg, MT_PG_SLOTS);
+                const size_t p0 = (size_t)pg * MT_PG_SLOTS;
+                if (j < hp) {
+                    W.opos -= pm.obs;
+                    W.rows -= ns;
+                }
+                const int before = W.opos;
+                tile_chunk<kMode>(W, Q, R.A + p0, R.B + p0, 0, ns, pos, prec, false);
+                if (j == hp && had_h && !W.hfound) {   // (obs and the page's rows disagree: never seen)
+                    walk = true;
+                    break;
+                }
+                W.hfound = true;
+                if (prec)
+                    W.opos = before;
+                else
+                    W.rows += ns;
+            }
+            if (walk) {
+                memset(&W.hit, 0, sizeof(W.hit));
+                W.hit.row = -1;
+                W.opos = W.rows = 0;
+                W.hfound = W.found = false;
+                total = -1;
+            }
+        }
+        if (walk) {
+            // from row 0: flat documents, by id, MT_LOCATE_ROW_WALK.  preceding stops at H's
+            // chunk, following at the first answer; by id every row is read
+            if (kMode == 0 && !prec && pos < 0) W.hfound = true;
+            int n_last = 0;
+            const v4i *A_last = nullptr;
+            const v4u *B_last = nullptr;
+            for (int rr = 0; rr < R.count(); rr++) {
+                if (kMode == 0 && (prec ? W.hfound : W.found)) break;
+                const v4i *A;
+                const v4u *Bv;
+                int n;
+                R.get(rr, A, Bv, n);
+                if (R.paged) n = min(n, MT_PG_SLOTS);
+                for (int base = 0; base < n; base += MT_WAVE) {
+                    if (kMode == 0 && (prec ? W.hfound : W.found)) break;
+                    tile_chunk<kMode>(W, Q, A, Bv, base, n, pos, prec, false);
+                }
+                W.rows += n;
+                n_last = n;   // (the last page, rows or none: the descent takes the last child)
+                A_last = A;
+                B_last = Bv;
+            }
+            // following, pos == length: no H was found and the whole document was walked
+            if (kMode == 0 && !prec && !W.hfound && pos == W.opos && n_last > 0) {
+                const int base = ((n_last - 1) / MT_WAVE) * MT_WAVE;
+                W.rows -= n_last;
+                // (the chunk's rows before the last one add up to length - its own: opos before it)
+                int before = 0;
+                {
+                    const int i = base + lane();
+                    const v4i a = A_last[i < n_last ? i : 0];
+                    before = wave_sum(i < n_last ? obs_len(a) : 0);
+                }
+                W.opos -= before;
+                tile_chunk<kMode>(W, Q, A_last, B_last, base, n_last, pos, prec, true);
+            }
+        }
+    }
+    if (lane() == 0) {
+        W.hit.flags = W.dup ? MT_MARK_DUP : 0u;
+        out[q] = W.hit;
+        examined[q] = W.examined;
+    }
+}
+
 // ============================================================================ host side
 // ---------------------------------------------------------------- live-client reconnect
 // regeneratePendingOp for the oldest pending segment group of one document (one wave):
@@ -1227,7 +1498,7 @@ __global__ void __launch_bounds__(MT_WAVE) k_regen(DevState st, int doc, mt_rege
 
 // Device time of a bulk read-out's kernels: up to two brackets of HIP events, created on first
 // use; `timed` counts the brackets of the last read-out whose kernels have finished
-// (read_timer: mt_last_text_ms, mt_last_props_ms, mt_last_locate, mt_last_dlog_ms).
+// (read_timer: mt_last_text_ms, mt_last_props_ms, mt_last_locate, mt_last_dlog_ms, mt_last_tiles).
 struct ReadTimer {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     int timed = 0;
@@ -1257,10 +1528,11 @@ struct mt_handle {
     bool load_timed = false;   // ev_load / ev_load1 bracket the last snapshot load's kernels
     // mt_get_texts, mt_get_prop_runs_bulk: around the counting pass, around the gather; the bulk
     // segment read-outs: around their kernel
-    ReadTimer tm_txt, tm_prp, tm_loc, tm_dlg;
+    ReadTimer tm_txt, tm_prp, tm_loc, tm_dlg, tm_tile;
     uint32_t *d_rst = nullptr;   // mt_delta_log_reset_docs: the listed documents (rst_cap of them)
     uint32_t rst_cap = 0;
     int64_t loc_n = 0, loc_host = 0;   // queries of the last segment read-out, of them answered by the host path
+    int64_t tile_n = 0, tile_rows = 0;   // queries of the last marker query, rows its kernel examined
     // documents per workgroup of the LDS-tier replay (env MT_WPG=2 for two): measured on C2
     // the CU saturates at 16 resident documents (16 -> 18 per CU: 61.8 -> 64.6 ms)
     int wpg = 1;
@@ -1836,7 +2108,7 @@ void mt_destroy(mt_handle *h) {
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->ev_load) hipEventDestroy(h->ev_load);
     if (h->ev_load1) hipEventDestroy(h->ev_load1);
-    for (ReadTimer *t : {&h->tm_txt, &h->tm_prp, &h->tm_loc, &h->tm_dlg}) t->destroy();
+    for (ReadTimer *t : {&h->tm_txt, &h->tm_prp, &h->tm_loc, &h->tm_dlg, &h->tm_tile}) t->destroy();
     if (h->d_rst) hipFree(h->d_rst);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -4059,6 +4331,143 @@ int mt_last_locate(mt_handle *h, int64_t *out, float *ms) {
     float t[2] = {0.f, 0.f};
     if (ms) {
         const int rc = read_timer(h, h->tm_loc, t);
+        *ms = t[0];
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- bulk marker queries
+// mt_find_tiles / mt_find_markers_by_id: one k_tiles launch.  Everything invalid is refused here,
+// before the launch; the kernel has no host path.
+static int tiles(mt_handle *h, const char *name, int mode, uint32_t n, const uint32_t *docs, const int32_t *pos,
+                 const uint8_t *preceding, const uint32_t *label, uint32_t key, uint32_t n_labels,
+                 const uint32_t *label_off, const uint32_t *label_vals, const uint32_t *id_val, mt_seg_hit *out,
+                 void *out_dev, bool device) {
+    if (!h) return MT_E_INVALID;
+    if (h->live) {
+        h->err = std::string(name) + ": not built for live handles";
+        return MT_E_INVALID;
+    }
+    if (n && (device ? !out_dev : !out)) return MT_E_INVALID;
+    if (n && (mode == 0 ? (!pos || !label) : !id_val)) return MT_E_INVALID;
+    if (mode == 0 && (!label_off || (n_labels && label_off[n_labels] && !label_vals))) return MT_E_INVALID;
+    const int bad = check_queries(h, name, n, docs);
+    if (bad) return bad;
+    if (mode == 0) {
+        // the label table: offsets ascending from 0, every set strictly ascending plain ids
+        if (label_off[0] != 0u) {
+            h->err = std::string(name) + ": label offsets do not start at 0";
+            return MT_E_INVALID;
+        }
+        for (uint32_t l = 0; l < n_labels; l++) {
+            if (label_off[l + 1] < label_off[l]) {
+                h->err = std::string(name) + ": label " + std::to_string(l) + ": offsets are not monotonic";
+                return MT_E_INVALID;
+            }
+            for (uint32_t j = label_off[l]; j < label_off[l + 1]; j++) {
+                const uint32_t v = label_vals[j];
+                if (v == MT_VAL_NULL || v == MT_VAL_UNDEF || (v & (MT_VAL_FALSY_BIT | MT_VAL_NOMATCH_BIT))) {
+                    h->err = std::string(name) + ": label " + std::to_string(l) + ": value id " + std::to_string(v) +
+                             " carries flag bits or is null / undefined";
+                    return MT_E_INVALID;
+                }
+                if (j > label_off[l] && label_vals[j - 1] >= v) {
+                    h->err = std::string(name) + ": label " + std::to_string(l) + ": value ids are not sorted";
+                    return MT_E_INVALID;
+                }
+            }
+        }
+        for (uint32_t q = 0; q < n; q++) {
+            if (pos[q] < -1) {
+                h->err = std::string(name) + ": query " + std::to_string(q) + ": position below -1 (undefined)";
+                return MT_E_INVALID;
+            }
+            if (label[q] >= n_labels) {
+                h->err = std::string(name) + ": query " + std::to_string(q) + ": no label " + std::to_string(label[q]);
+                return MT_E_INVALID;
+            }
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    SETTLE(h);
+    ReadTimer &tm = h->tm_tile;
+    tm.timed = 0;
+    h->tile_n = n;
+    h->tile_rows = 0;
+    if (n == 0) return 0;
+    // sel: label index | preceding << 31 (tiles), the id's value id (by id; flag bits dropped)
+    std::vector<uint32_t> sel(n);
+    for (uint32_t q = 0; q < n; q++)
+        sel[q] = mode == 0 ? (label[q] | ((!preceding || preceding[q]) ? 0x80000000u : 0u))
+                           : (id_val[q] == MT_VAL_NULL ? MT_VAL_NULL : id_val[q] & ~(MT_VAL_FALSY_BIT | MT_VAL_NOMATCH_BIT));
+    // extra: examined[n], the label table (offsets, values), the records (host results)
+    const size_t up8 = 7;
+    const size_t ex_b = ((size_t)n * 4 + up8) & ~up8;
+    const size_t off_b = mode == 0 ? (((size_t)n_labels + 1) * 4 + up8) & ~up8 : 0;
+    const size_t val_b = mode == 0 ? ((size_t)label_off[n_labels] * 4 + up8) & ~up8 : 0;
+    const size_t hit_b = device ? 0 : (size_t)n * sizeof(mt_seg_hit);
+    QueryCols qc;
+    HIPCHK(h, qc.upload(n, {docs, pos, sel.data()}, hit_b + ex_b + off_b + val_b));
+    mt_seg_hit *d_hit = device ? (mt_seg_hit *)out_dev : (mt_seg_hit *)qc.extra;
+    int32_t *d_ex = (int32_t *)(qc.extra + hit_b);
+    uint32_t *d_off = (uint32_t *)(qc.extra + hit_b + ex_b), *d_val = (uint32_t *)(qc.extra + hit_b + ex_b + off_b);
+    if (mode == 0) {
+        HIPCHK(h, hipMemcpy(d_off, label_off, ((size_t)n_labels + 1) * 4, hipMemcpyHostToDevice));
+        if (label_off[n_labels])
+            HIPCHK(h, hipMemcpy(d_val, label_vals, (size_t)label_off[n_labels] * 4, hipMemcpyHostToDevice));
+    }
+    const uint32_t *d_docs = (const uint32_t *)qc.col[0], *d_sel = (const uint32_t *)qc.col[2];
+    const int32_t *d_pos = (const int32_t *)qc.col[1];
+    // MT_LOCATE_ROW_WALK=1: walk from row 0 (the A/B of tools/tile_probe.py)
+    const char *rw = getenv("MT_LOCATE_ROW_WALK");
+    const int skip = !(rw && rw[0] == '1');
+    HIPCHK(h, tm.begin(0, h->stream));
+    if (mode == 0)
+        hipLaunchKernelGGL(k_tiles<0>, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_pos, d_sel, key, d_off,
+                           d_val, skip, d_hit, d_ex);
+    else
+        hipLaunchKernelGGL(k_tiles<1>, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_pos, d_sel, key,
+                           (const uint32_t *)nullptr, (const uint32_t *)nullptr, skip, d_hit, d_ex);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, tm.end(0, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    tm.timed = 1;
+    std::vector<int32_t> ex(n);
+    HIPCHK(h, hipMemcpy(ex.data(), d_ex, (size_t)n * 4, hipMemcpyDeviceToHost));
+    for (uint32_t q = 0; q < n; q++) h->tile_rows += ex[q];
+    if (hit_b) HIPCHK(h, hipMemcpy(out, d_hit, hit_b, hipMemcpyDeviceToHost));
+    return 0;
+}
+int mt_find_tiles(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *pos, const uint8_t *preceding,
+                  const uint32_t *label, uint32_t tile_key, uint32_t n_labels, const uint32_t *label_off,
+                  const uint32_t *label_vals, mt_seg_hit *out) {
+    return tiles(h, "mt_find_tiles", 0, n, docs, pos, preceding, label, tile_key, n_labels, label_off, label_vals, nullptr,
+                 out, nullptr, false);
+}
+int mt_find_tiles_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *pos, const uint8_t *preceding,
+                         const uint32_t *label, uint32_t tile_key, uint32_t n_labels, const uint32_t *label_off,
+                         const uint32_t *label_vals, void *out_dev) {
+    return tiles(h, "mt_find_tiles_device", 0, n, docs, pos, preceding, label, tile_key, n_labels, label_off, label_vals,
+                 nullptr, nullptr, out_dev, true);
+}
+int mt_find_markers_by_id(mt_handle *h, uint32_t n, const uint32_t *docs, uint32_t id_key, const uint32_t *id_val,
+                          mt_seg_hit *out) {
+    return tiles(h, "mt_find_markers_by_id", 1, n, docs, nullptr, nullptr, nullptr, id_key, 0, nullptr, nullptr, id_val, out,
+                 nullptr, false);
+}
+int mt_find_markers_by_id_device(mt_handle *h, uint32_t n, const uint32_t *docs, uint32_t id_key, const uint32_t *id_val,
+                                 void *out_dev) {
+    return tiles(h, "mt_find_markers_by_id_device", 1, n, docs, nullptr, nullptr, nullptr, id_key, 0, nullptr, nullptr,
+                 id_val, nullptr, out_dev, true);
+}
+int mt_last_tiles(mt_handle *h, int64_t *out, float *ms) {
+    if (!h || !out) return MT_E_INVALID;
+    out[0] = h->tile_n;
+    out[1] = h->tile_rows;
+    float t[2] = {0.f, 0.f};
+    if (ms) {
+        const int rc = read_timer(h, h->tm_tile, t);
         *ms = t[0];
         if (rc) return rc;
     }

@@ -704,6 +704,77 @@ napi_value LocateSegments(napi_env env, napi_callback_info info) { return locate
 napi_value LocateUids(napi_env env, napi_callback_info info) { return locate(env, info, 1); }
 napi_value ResolveRemotePositions(napi_env env, napi_callback_info info) { return locate(env, info, 2); }
 
+// findTiles(h, docs, pos, preceding, label, tileKey, labelOff, labelVals) / findMarkersById(h, docs,
+// idKey, idVals) -> Int32Array, 12 words per query: the mt_seg_hit records of mt_find_tiles /
+// mt_find_markers_by_id.  docs, label, labelOff, labelVals, idVals: Uint32Arrays; pos: Int32Array
+// (-1: undefined); preceding: Uint8Array; one entry per query (labelOff: labels + 1 offsets).
+bool get_typed(napi_env env, napi_value v, napi_typedarray_type want, void **ptr, size_t *len) {
+    napi_typedarray_type t;
+    napi_value ab;
+    size_t off;
+    if (napi_get_typedarray_info(env, v, &t, len, ptr, &ab, &off) != napi_ok || t != want) {
+        napi_throw_type_error(env, nullptr, "marker queries: docs, label, labelOff, labelVals and idVals are Uint32Arrays, "
+                                            "pos an Int32Array, preceding a Uint8Array");
+        return false;
+    }
+    if (!*ptr) *ptr = len;   // (an empty array: any non-null pointer, never read)
+    return true;
+}
+napi_value FindTiles(napi_env env, napi_callback_info info) {
+    napi_value argv[8];
+    if (!get_args(env, info, 8, argv)) return nullptr;
+    Handle *hd = get_handle(env, argv[0]);
+    if (!hd) return nullptr;
+    const napi_typedarray_type want[7] = {napi_uint32_array, napi_int32_array, napi_uint8_array, napi_uint32_array,
+                                          napi_uint32_array, napi_uint32_array, napi_uint32_array};
+    const int at[6] = {1, 2, 3, 4, 6, 7};   // docs, pos, preceding, label, labelOff, labelVals
+    void *ptrs[6];
+    size_t lens[6];
+    for (int i = 0; i < 6; i++)
+        if (!get_typed(env, argv[at[i]], want[i < 4 ? i : 4], &ptrs[i], &lens[i])) return nullptr;
+    const uint32_t key = (uint32_t)get_i32(env, argv[5]);
+    const size_t n = lens[0];
+    if (lens[1] != n || lens[2] != n || lens[3] != n || lens[4] == 0 ||
+        ((const uint32_t *)ptrs[4])[lens[4] - 1] > lens[5]) {
+        napi_throw_range_error(env, nullptr, "findTiles: one entry per query; labelOff ends within labelVals");
+        return nullptr;
+    }
+    void *d;
+    napi_value ab, arr;
+    const size_t words = n * (sizeof(mt_seg_hit) / 4);
+    NAPI_CALL(env, napi_create_arraybuffer(env, std::max<size_t>(words, 1) * 4, &d, &ab));
+    const int rc = mt_find_tiles(hd->h, (uint32_t)n, (const uint32_t *)ptrs[0], (const int32_t *)ptrs[1],
+                                 (const uint8_t *)ptrs[2], (const uint32_t *)ptrs[3], key, (uint32_t)(lens[4] - 1),
+                                 (const uint32_t *)ptrs[4], (const uint32_t *)ptrs[5], (mt_seg_hit *)d);
+    if (rc) return throw_rc(env, hd, rc, "mt_find_tiles");
+    NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, words, ab, 0, &arr));
+    return arr;
+}
+napi_value FindMarkersById(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    Handle *hd = get_handle(env, argv[0]);
+    if (!hd) return nullptr;
+    void *docs, *vals;
+    size_t n, nv;
+    if (!get_typed(env, argv[1], napi_uint32_array, &docs, &n) || !get_typed(env, argv[3], napi_uint32_array, &vals, &nv))
+        return nullptr;
+    const uint32_t key = (uint32_t)get_i32(env, argv[2]);
+    if (nv != n) {
+        napi_throw_range_error(env, nullptr, "findMarkersById: one id per query");
+        return nullptr;
+    }
+    void *d;
+    napi_value ab, arr;
+    const size_t words = n * (sizeof(mt_seg_hit) / 4);
+    NAPI_CALL(env, napi_create_arraybuffer(env, std::max<size_t>(words, 1) * 4, &d, &ab));
+    const int rc = mt_find_markers_by_id(hd->h, (uint32_t)n, (const uint32_t *)docs, key, (const uint32_t *)vals,
+                                         (mt_seg_hit *)d);
+    if (rc) return throw_rc(env, hd, rc, "mt_find_markers_by_id");
+    NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, words, ab, 0, &arr));
+    return arr;
+}
+
 // getDeltaLog(h, doc) -> Int32Array (only with deltaLogCapacity > 0; oracle layout)
 napi_value GetDeltaLog(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -1054,7 +1125,8 @@ napi_value Init(napi_env env, napi_value exports) {
                {"applyOpsAsync", ApplyOpsAsync},         {"getContainingSegment", GetContainingSegment},
                {"getSegmentByUid", GetSegmentByUid},     {"getViewLengths", GetViewLengths},
                {"extractSnapshots", ExtractSnapshots},   {"locateSegments", LocateSegments},
-               {"locateUids", LocateUids},               {"resolveRemotePositions", ResolveRemotePositions}};
+               {"locateUids", LocateUids},               {"resolveRemotePositions", ResolveRemotePositions},
+               {"findTiles", FindTiles},                 {"findMarkersById", FindMarkersById}};
     for (auto &f : fns) {
         napi_value v;
         NAPI_CALL(env, napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v));

@@ -125,6 +125,26 @@ class Interner {
         }
         return (i | (v ? 0 : VAL_FALSY_BIT) | (noMatch(v) ? VAL_NOMATCH_BIT : 0)) >>> 0;
     }
+    /** The id (without flag bits) of a value already interned; undefined when it never was. */
+    knownVal(v) { return this.valIds.get(canonical(v)); }
+    /**
+     * Ids (ascending) of the interned values that yield `label` when JavaScript iterates them
+     * (mergeTree.ts:626-635): arrays holding it, strings holding it as a character.  Kept per
+     * label and extended when the interner has grown.
+     */
+    labelIds(label) {
+        if (this.labelSets === undefined) { this.labelSets = new Map(); }
+        let e = this.labelSets.get(label);
+        if (e === undefined) { e = { seen: 0, ids: [] }; this.labelSets.set(label, e); }
+        for (; e.seen < this.vals.length; e.seen++) {
+            const v = this.vals[e.seen];
+            if ((Array.isArray(v) && v.includes(label)) ||
+                (typeof v === "string" && label.length === 1 && v.includes(label))) {
+                e.ids.push(e.seen);
+            }
+        }
+        return e.ids;
+    }
     keyName(id) { return this.keys[id]; }
     value(id) {
         if (id === VAL_NULL) { return null; }

@@ -421,6 +421,55 @@ class GpuMergeTreeBatch {
         return Array.from(r, (p) => (p < 0 ? undefined : p));
     }
 
+    _hit(w, o) {
+        if (w[o] < 0) { return undefined; }
+        const r = { row: w[o], uid: w[o + 1] >>> 0, position: w[o + 2], length: w[o + 5], seq: w[o + 6], clientId: w[o + 7],
+            markerRefType: w[o + 10], duplicate: (w[o + 11] & 2) !== 0 };
+        if (w[o + 8] !== -2147483648) { r.removedSeq = w[o + 8]; r.removedClientId = w[o + 9]; }
+        return r;
+    }
+
+    /**
+     * SharedString.findTile for many cursors in one launch (mt_find_tiles), in the replica's own
+     * view.  queries: [{doc, pos (undefined: none), label, preceding (default true)}].  Per query
+     * undefined when no tile marker carries the label on that side of the position, else {uid,
+     * row, position (the marker's), length, seq, clientId, removedSeq?, removedClientId?,
+     * markerRefType}.  Not built for live-client batches.
+     */
+    findTiles(queries) {
+        this.flush();
+        const names = Array.from(new Set(queries.map((q) => q.label))).sort();
+        const index = new Map(names.map((s, i) => [s, i]));
+        const sets = names.map((s) => this.interner.labelIds(s));
+        const off = new Uint32Array(names.length + 1);
+        sets.forEach((s, i) => { off[i + 1] = off[i] + s.length; });
+        const vals = Uint32Array.from([].concat(...sets));
+        // (a key the interner has never seen is held by no record)
+        const key = this.interner.keyIds.has("referenceTileLabels") ? this.interner.keyIds.get("referenceTileLabels") : VAL_NULL;
+        const w = native.findTiles(this.h, Uint32Array.from(queries, (q) => q.doc),
+            Int32Array.from(queries, (q) => (q.pos === undefined || q.pos === null ? -1 : q.pos)),
+            Uint8Array.from(queries, (q) => (q.preceding === undefined || q.preceding ? 1 : 0)),
+            Uint32Array.from(queries, (q) => index.get(q.label)), key, off, vals);
+        return queries.map((_, q) => this._hit(w, 12 * q));
+    }
+
+    /**
+     * SharedString.getMarkerFromId for many [{doc, id}] in one launch (mt_find_markers_by_id): the
+     * marker row, removed or not, whose markerId property is the id; undefined when no row of the
+     * tree carries it (the reference still returns a marker zamboni has unlinked).  `duplicate`:
+     * several rows carry the id and the first one in document order answers.
+     */
+    getMarkersFromIds(queries) {
+        this.flush();
+        const key = this.interner.keyIds.has("markerId") ? this.interner.keyIds.get("markerId") : VAL_NULL;
+        const ids = Uint32Array.from(queries, (q) => {
+            const v = q.id ? this.interner.knownVal(q.id) : undefined;   // (a falsy id is never mapped)
+            return v === undefined ? VAL_NULL : v;
+        });
+        const w = native.findMarkersById(this.h, Uint32Array.from(queries, (q) => q.doc), key, ids);
+        return queries.map((_, q) => this._hit(w, 12 * q));
+    }
+
     _recordProps(records, base, rec) {
         if (rec === 0xFFFFFFFF) { return undefined; }
         const at = base + rec, n = records[at];
@@ -780,6 +829,36 @@ class GpuClient {
     /** Client.getContainingSegment(pos) (client.ts:1006-1009, mergeTree.ts:1656-1667). */
     getContainingSegment(pos) {
         return this.mergeTree.getContainingSegment(pos, this.currentSeq, 0);
+    }
+
+    // a marker query's record as the document's object for that segment (its full read-out)
+    _markerObject(hit) {
+        const r = native.getSegmentByUid(this.batch.h, this.doc, hit.uid, this.currentSeq, 0);
+        return r === null ? undefined : this._segFromInfo(r);
+    }
+
+    /**
+     * Client.findTile(startPos, tileLabel, preceding) (client.ts:1075-1078, mergeTree.ts:1796-1822;
+     * SharedString.findTile, sharedString.ts:214): the nearest tile marker carrying the label at
+     * or before (preceding) / at or after startPos, as {tile, pos}; undefined when there is none.
+     * `tile` is the document's object for that segment, the one delta events carry.
+     */
+    findTile(startPos, tileLabel, preceding = true) {
+        this._sync();
+        const hit = this.batch.findTiles([{ doc: this.doc, pos: startPos, label: tileLabel, preceding }])[0];
+        if (hit === undefined) { return undefined; }
+        return { tile: this._markerObject(hit), pos: hit.position };
+    }
+
+    /**
+     * MergeTree.getMarkerFromId(id) (mergeTree.ts:1965; SharedString.getMarkerFromId,
+     * sharedString.ts:242): the marker whose markerId property is id, removed or not; undefined
+     * once zamboni has unlinked it (the reference keeps returning the detached object).
+     */
+    getMarkerFromId(id) {
+        this._sync();
+        const hit = this.batch.getMarkersFromIds([{ doc: this.doc, id }])[0];
+        return hit === undefined ? undefined : this._markerObject(hit);
     }
 
     /**

@@ -486,6 +486,57 @@ int mt_resolve_remote_positions(mt_handle *h, uint32_t n, const uint32_t *docs, 
    observer-view queries walk every row instead of skipping pages by their observer lengths and
    the uid map (the A/B of tools/cursor_probe.py; results are identical). */
 int mt_last_locate(mt_handle *h, int64_t *out /* [2] */, float *ms);
+/* ---- bulk marker queries: SharedString.findTile / getMarkerFromId (SEQ/sharedString.ts:214, :242;
+        MT/client.ts:1075, MT/mergeTree.ts:1796-1822, :1965) for n queries in one launch, one wave
+        per query, in the replica's own (observer) view.  Arguments and errors are
+        mt_locate_segments': the call settles the handle first; docs NULL: documents 0..n-1; a
+        document may repeat, in any order; failed documents answer from where they stopped; n == 0
+        is fine; everything invalid is refused before any launch and mt_last_error names the
+        query.  A live-client handle is refused (MT_E_INVALID): its local view holds unacked rows.
+        The record is mt_seg_hit: position == local_position == the marker's observer position,
+        offset 0, row -1 when there is no answer.
+   mt_find_tiles: a row qualifies for label l when it is a marker whose refType has the Tile bit
+        (1) and whose property set holds tile_key (the interned key "referenceTileLabels") with a
+        value of label l's set.  The label table: label l is the ascending value ids
+        label_vals[label_off[l] .. label_off[l + 1]) (label_off[0] == 0; ids without the
+        MT_VAL_*_BIT flags, neither MT_VAL_NULL nor MT_VAL_UNDEF) of the values that yield the
+        label when JavaScript iterates them with for...of: arrays holding it, strings holding it
+        as a character (MT/mergeTree.ts:620-635).  Any other truthy value makes the reference
+        throw; here such a row does not qualify.
+        With H the first row whose inclusive observer-length prefix exceeds pos[q]:
+        preceding (search with tileShift, :1030-1069, :1830-1862): the last qualifying visible row
+        at or before H; with no H (pos >= length, or pos -1: undefined) the last one of the
+        document.  Following (preceding[q] == 0, backwardSearch :1864-1907): pos > length:
+        nothing; pos < length: the first qualifying visible row at or after H; pos -1: the first
+        one of the document; pos == length: the document's last row, removed or not, when it
+        qualifies (the descent takes the last child at every level and the leaf is asked no
+        visibility), else nothing.
+        MT_E_INVALID: pos < -1, label[q] >= n_labels, offsets that do not ascend from 0, a label
+        set not strictly ascending, a value id with flag bits or MT_VAL_NULL / MT_VAL_UNDEF.
+   mt_find_markers_by_id: the marker row, removed or not, whose property set holds id_key (the
+        interned key "markerId") with the value id id_val[q] (without flag bits; MT_VAL_NULL: an
+        id no document holds, row -1).  Two deviations from the reference's idToSegment map: once
+        zamboni has unlinked a removed marker the reference still returns the detached object,
+        here the answer is row -1; with the same id on several markers the reference answers with
+        whichever block was updated last, here the answer is the first row in document order and
+        flags carries MT_MARK_DUP. ---- */
+#define MT_MARK_DUP 2u           /* mt_seg_hit.flags: more than one marker row carries the id */
+int mt_find_tiles(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *pos /* -1: undefined */,
+                  const uint8_t *preceding /* NULL: all 1 */, const uint32_t *label /* index per query */,
+                  uint32_t tile_key, uint32_t n_labels, const uint32_t *label_off, const uint32_t *label_vals,
+                  mt_seg_hit *out);
+int mt_find_tiles_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *pos,
+                         const uint8_t *preceding, const uint32_t *label, uint32_t tile_key, uint32_t n_labels,
+                         const uint32_t *label_off, const uint32_t *label_vals, void *out_dev);
+int mt_find_markers_by_id(mt_handle *h, uint32_t n, const uint32_t *docs, uint32_t id_key,
+                          const uint32_t *id_val, mt_seg_hit *out);
+int mt_find_markers_by_id_device(mt_handle *h, uint32_t n, const uint32_t *docs, uint32_t id_key,
+                                 const uint32_t *id_val, void *out_dev);
+/* The most recent bulk marker query: out[2] = {queries, rows its kernel examined}; *ms (nullable)
+   the kernel's device time (HIP events).  MT_LOCATE_ROW_WALK=1 makes mt_find_tiles walk from row
+   0 instead of finding H's page by the directory and moving away from it page by page (the A/B
+   of tools/tile_probe.py; results are identical). */
+int mt_last_tiles(mt_handle *h, int64_t *out /* [2] */, float *ms);
 /* Debug: raw segment records (8 u32 per segment: segA then segB) and the 32-word header. */
 int mt_debug_raw(mt_handle *h, uint32_t doc, uint32_t *rows, uint32_t cap_rows, uint32_t *n_rows,
                  int32_t *hdr_words);

@@ -860,6 +860,78 @@ class MergeTreeBatch:
         self._check(self.lib.mt_last_tiles(self.h, _native.ptr(out), ctypes.byref(ms)), "mt_last_tiles")
         return int(out[0]), int(out[1]), float(ms.value)
 
+    # bulk ranged segment walk (mt_walk_segments): SharedSegmentSequence.walkSegments(handler,
+    # start, end) for many (doc, start, end) queries in one counting pass and one gather
+    def _walk_queries(self, docs, start, end, text, props):
+        """(n, docs, start, end, what) as mt_walk_segments takes them; None entries of start are
+        0, of end the document's length."""
+        if isinstance(start, (list, tuple)):
+            start = [0 if s is None else s for s in start]
+        n, docs, start, end, _ = self._text_queries(docs, start, end, 0)
+        what = (_native.MT_WALK_TEXT if text else 0) | (_native.MT_WALK_PROPS if props else 0)
+        return n, docs, start, end, what
+
+    def walk_segments(self, docs=None, start=None, end=None, text=True, props=True):
+        """(row_off, rows, text_off, text, word_off, records): query q's visited rows, in document
+        order, are rows[row_off[q]:row_off[q + 1]] (WALK_ROW_DTYPE).  A row is visited when its
+        observer length is > 0, its position is < end and its position + length is > start
+        (nothing is clamped: start == end inside a segment visits it).  A text row's whole text
+        is text[text_off[q] + row.text:][:row.length] (UTF-16 units), its property record
+        [count, (key, value) x count] starts at records[word_off[q] + row.props]; either field
+        is 0xFFFFFFFF when there is none or it was not asked for.  Queries as in get_texts."""
+        n, docs, start, end, what = self._walk_queries(docs, start, end, text, props)
+        row_off, text_off, word_off = (np.zeros(n + 1, dtype=np.int64) for _ in range(3))
+        args = (self.h, n, _native.ptr(docs), _native.ptr(start), _native.ptr(end), what, _native.ptr(row_off),
+                _native.ptr(text_off), _native.ptr(word_off))
+        self._check(self.lib.mt_walk_segments(*args, None, 0, None, 0, None, 0), "mt_walk_segments")
+        nr, nt, nw = int(row_off[n]), int(text_off[n]), int(word_off[n])
+        rows = np.zeros(max(nr, 1), dtype=_native.WALK_ROW_DTYPE)
+        units = np.zeros(max(nt, 1), dtype=np.uint16)
+        recs = np.zeros(max(nw, 1), dtype=np.uint32)
+        self._check(self.lib.mt_walk_segments(*args, _native.ptr(rows), nr, _native.ptr(units), nt, _native.ptr(recs), nw),
+                    "mt_walk_segments")
+        return row_off, rows[:nr], text_off, units[:nt], word_off, recs[:nw]
+
+    def walk_segments_device(self, docs=None, start=None, end=None, text=True, props=True, out=None):
+        """walk_segments with the results left on the handle's device: (row_off, rows, text_off,
+        text, word_off, records) torch tensors (int64 [n + 1] offsets; rows int32 [R, 12] holding
+        the records' words, text int16, records int32).  out: (rows, text, records) tensors of
+        those types on that device to fill (at least the results' sizes); the results are then
+        their leading slices.  (torch is imported before the first handle is created, as for
+        get_texts_device.)"""
+        import torch
+        n, docs, start, end, what = self._walk_queries(docs, start, end, text, props)
+        dev = torch.device("cuda", self.device)
+        row_off, text_off, word_off = (torch.empty(n + 1, dtype=torch.int64, device=dev) for _ in range(3))
+        args = (self.h, n, _native.ptr(docs), _native.ptr(start), _native.ptr(end), what,
+                ctypes.c_void_p(row_off.data_ptr()), ctypes.c_void_p(text_off.data_ptr()),
+                ctypes.c_void_p(word_off.data_ptr()))
+        if out is None:
+            self._check(self.lib.mt_walk_segments_device(*args, None, 0, None, 0, None, 0), "mt_walk_segments_device")
+            rows = torch.empty((max(int(row_off[n]), 1), 12), dtype=torch.int32, device=dev)
+            units = torch.empty(max(int(text_off[n]), 1), dtype=torch.int16, device=dev)
+            recs = torch.empty(max(int(word_off[n]), 1), dtype=torch.int32, device=dev)
+        else:
+            rows, units, recs = out
+            for t, dt in ((rows, torch.int32), (units, torch.int16), (recs, torch.int32)):
+                if t.dtype != dt or t.device != dev or not t.is_contiguous():
+                    raise ValueError("walk_segments_device: out holds contiguous int32 / int16 / int32 tensors on "
+                                     "the handle's device")
+            if rows.dim() != 2 or rows.shape[1] != 12 or units.dim() != 1 or recs.dim() != 1:
+                raise ValueError("walk_segments_device: out is (rows [R, 12], text [units], records [words])")
+        self._check(self.lib.mt_walk_segments_device(*args, ctypes.c_void_p(rows.data_ptr()), rows.shape[0],
+                                                     ctypes.c_void_p(units.data_ptr()), units.numel(),
+                                                     ctypes.c_void_p(recs.data_ptr()), recs.numel()),
+                    "mt_walk_segments_device")
+        return (row_off, rows[: int(row_off[n])], text_off, units[: int(text_off[n])], word_off,
+                recs[: int(word_off[n])])
+
+    def last_walk(self):
+        """Device time (ms) of the last walk_segments call's counting pass and gather."""
+        out = np.zeros(2, dtype=np.float32)
+        self._check(self.lib.mt_last_walk_ms(self.h, _native.ptr(out)), "mt_last_walk_ms")
+        return float(out[0]), float(out[1])
+
     def get_prop_runs(self, doc):
         nr, nw = ctypes.c_uint32(), ctypes.c_uint32()
         self._check(self.lib.mt_get_prop_runs(self.h, doc, None, 0, ctypes.byref(nr), None, 0,

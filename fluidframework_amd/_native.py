@@ -52,6 +52,12 @@ SEG_HIT_DTYPE = np.dtype([("row", "<i4"), ("uid", "<u4"), ("position", "<i4"), (
 MT_HIT_HOST = 1
 MT_MARK_DUP = 2   # bulk marker queries: more than one marker row carries the id
 
+# mt_walk_row (include/mt_replay.h): one visited row of the bulk segment walk
+WALK_ROW_DTYPE = np.dtype([("row", "<i4"), ("uid", "<u4"), ("position", "<i4"), ("length", "<i4"), ("seq", "<i4"),
+                           ("client", "<i4"), ("marker_ref_type", "<i4"), ("text", "<u4"), ("props", "<u4"),
+                           ("start", "<i4"), ("end", "<i4"), ("flags", "<u4")])
+MT_WALK_TEXT, MT_WALK_PROPS = 1, 2
+
 # mt_delta_range (include/mt_replay.h): one delta segment of mt_get_delta_logs' rows
 DELTA_RANGE_DTYPE = np.dtype([("query", "<i4"), ("record", "<i4"), ("seq", "<i4"), ("kind", "<i4"),
                               ("position", "<i4"), ("length", "<i4"), ("word", "<i4"), ("uid", "<u4")])
@@ -171,6 +177,9 @@ SIGNATURES = [
     ("mt_find_markers_by_id", _I, [_P, _U32, _P, _U32, _P, _P]),
     ("mt_find_markers_by_id_device", _I, [_P, _U32, _P, _U32, _P, _P]),
     ("mt_last_tiles", _I, [_P, _P, _P]),
+    ("mt_walk_segments", _I, [_P, _U32, _P, _P, _P, _U32, _P, _P, _P, _P, _U64, _P, _U64, _P, _U64]),
+    ("mt_walk_segments_device", _I, [_P, _U32, _P, _P, _P, _U32, _P, _P, _P, _P, _U64, _P, _U64, _P, _U64]),
+    ("mt_last_walk_ms", _I, [_P, _P]),
 ]
 
 _lib = None

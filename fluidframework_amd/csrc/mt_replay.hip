@@ -798,6 +798,259 @@ __global__ void __launch_bounds__(MT_WAVE) k_props_gather(DevState st, int nq, c
     if (open_row >= 0 && open_row < room_r && lane() == 0) rows[3 * open_row + 1] = (uint32_t)(Q.s + done - open_pos);
 }
 
+// ---------------------------------------------------------------- bulk ranged segment walk
+// Client.walkSegments(handler, start, end) (MT/client.ts:276-285 -> MergeTree.mapRange / nodeMap,
+// MT/mergeTree.ts:2830-2840, :2936-2998) for many (doc, start, end) queries in the replica's own
+// view: one wave per query, the rows in chunks of 64 as k_text_count walks them.  nodeMap enters
+// a child -- a block or a leaf -- when (end > 0) && (len > 0) && (start < len) holds on the start
+// and end shifted by the lengths before it, so a row at observer position pos of observer length
+// len is visited iff len > 0, pos < end and pos + len > start; nothing is clamped, start == end
+// inside a row visits it and start > end visits the row that spans both.
+// The count pass gives per query the visited rows, the units of the visited text rows (whole
+// texts, not the clipped part: the handler gets the segment) and the words of their property
+// records, and the query's end as the leaf action sees it (an undefined end is the document's
+// length, which the walk to the document's end has summed); the gather repeats the walk.
+static_assert(sizeof(mt_walk_row) == 48, "mt_walk_row size");
+struct WalkQuery {         // wave-uniform
+    int doc, s, e;         // e: 0x7FFFFFFF while an undefined end is not yet resolved
+    bool open;             // the end is undefined (NULL or < 0)
+};
+__device__ static WalkQuery walk_query(const DevState &st, int q, const uint32_t *docs, const int32_t *start,
+                                       const int32_t *end) {
+    WalkQuery Q;
+    Q.doc = docs ? (int)docs[q] : q;
+    Q.s = start ? max(start[q], 0) : 0;   // (the host refuses a negative start)
+    const int e = end ? end[q] : -1;
+    Q.open = e < 0;
+    Q.e = Q.open ? 0x7FFFFFFF : e;
+    if (Q.doc < 0 || Q.doc >= st.n_docs) {   // (the host refuses these)
+        Q.doc = 0;
+        Q.e = 0;
+        Q.open = false;
+    }
+    return Q;
+}
+// Where the walk starts: row 0, or on a paged document the first page whose inclusive
+// PageMeta.obs prefix exceeds start (k_locate's directory scan, 64 positions at a time) -- every
+// row before that page ends at or before start.  r0: the range (page) index, pos / rows: the
+// observer length and the rows before it; no such page: r0 = the range count (nothing to visit,
+// pos is the document's length).
+__device__ __forceinline__ void walk_seek(const SegRanges &R, int s, int skip, int &r0, int &pos, int &rows) {
+    r0 = pos = rows = 0;
+    if (!R.paged || !skip) return;
+    bool at = false;
+    for (int base = 0; !at && base < R.nr; base += MT_WAVE) {
+        const int j = base + lane();
+        const bool v = j < R.nr;
+        const int pg = R.dir[v ? j : 0];
+        const PageMeta pm = R.meta[pg];
+        const int ob = v ? pm.obs : 0, ns = v ? (int)pm.nseg : 0;
+        const int oin = wave_scan_incl(ob), nin = wave_scan_incl(ns);
+        const u64 m = ballot(v & (pos + oin > s));
+        if (m) {
+            const int l = first_lane(m);
+            r0 = base + l;
+            pos += bcast(oin - ob, l);
+            rows += bcast(nin - ns, l);
+            at = true;
+        } else {
+            pos += bcast(oin, 63);
+            rows += bcast(nin, 63);
+        }
+    }
+    if (!at) r0 = R.nr;
+}
+struct WalkLane {
+    bool vis;        // the lane's row is visited
+    int p0;          // its observer position
+    int units;       // text units it contributes (its whole text; 0: a marker, or text not asked for)
+    int wc;          // words of its property record (0: none, or not asked for)
+    v4i a;
+    v4u b;
+};
+// lane's row i of a range of n rows; pos is the chunk's first position, advanced past it.  A row
+// past the count is loaded from index 0 and masked; the record's count word is loaded
+// unconditionally (record 0 for a handle outside the arena) and masked.
+__device__ __forceinline__ WalkLane walk_chunk(const v4i *A, const v4u *Bv, int i, int n, const WalkQuery &Q,
+                                               uint32_t what, const uint32_t *pr, uint32_t P, int &pos) {
+    WalkLane L;
+    const bool v = i < n;
+    const int ic = v ? i : 0;
+    L.a = A[ic];
+    L.b = Bv[ic];
+    if (!v) {
+        L.a = v4i{0, 0, MT_RSEQ_NONE, 0};
+        L.b = v4u{0u, 0u, 0u, 0u};
+    }
+    const int ol = obs_len(L.a);
+    const int incl = wave_scan_incl(ol);
+    L.p0 = pos + incl - ol;
+    pos += bcast(incl, 63);
+    L.vis = v & (ol > 0) & (L.p0 < Q.e) & (L.p0 + ol > Q.s);
+    const bool marker = (L.b.z & MT_MARKER_BIT) != 0u;
+    L.units = (L.vis & !marker & ((what & MT_WALK_TEXT) != 0u)) ? ol : 0;
+    const uint32_t hi = L.b.y < P ? L.b.y : 0u;
+    const uint32_t c = pr[(size_t)hi * MT_PREC];
+    const bool ok = (hi != 0u) & (c <= (uint32_t)MT_KMAX);
+    L.wc = (L.vis & ok & ((what & MT_WALK_PROPS) != 0u)) ? 1 + 2 * (int)c : 0;
+    return L;
+}
+__global__ void __launch_bounds__(MT_WAVE) k_walk_count(DevState st, int nq, const uint32_t *docs, const int32_t *start,
+                                                        const int32_t *end, uint32_t what, int skip, int64_t *n_rows,
+                                                        int64_t *n_units, int64_t *n_words, int32_t *end_seen) {
+    const int q = blockIdx.x;
+    if (q >= nq) return;
+    const WalkQuery Q = walk_query(st, q, docs, start, end);
+    int rows_n = 0, units = 0, words = 0, pos = 0;
+    if (Q.e > 0) {
+        const DocHdr h = st.hdr[Q.doc];
+        const SegRanges R = seg_ranges(st, Q.doc, h);
+        const PagedBase ar = doc_paged(st, Q.doc);   // (the arenas of the document's region)
+        const uint32_t P = (uint32_t)ar.P;
+        const uint32_t *pr = ar.props + (size_t)h.props_half * P * MT_PREC;
+        int r0, rows;
+        walk_seek(R, Q.s, skip, r0, pos, rows);
+        for (int r = r0; r < R.count() && pos < Q.e; r++) {
+            const v4i *A;
+            const v4u *Bv;
+            int n;
+            R.get(r, A, Bv, n);
+            for (int base = 0; base < n && pos < Q.e; base += MT_WAVE) {
+                const WalkLane L = walk_chunk(A, Bv, base + lane(), n, Q, what, pr, P, pos);
+                rows_n += __popcll(ballot(L.vis));
+                units += L.units;
+                words += L.wc;
+            }
+        }
+        units = wave_sum(units);
+        words = wave_sum(words);
+    }
+    if (lane() == 0) {
+        n_rows[q] = rows_n;
+        n_units[q] = units;
+        n_words[q] = words;
+        end_seen[q] = Q.open ? pos : Q.e;   // (an open walk ran to the document's end: pos is its length)
+    }
+}
+// Writes query q's records at rows[row_off[q] ..), its texts at text[text_off[q] ..) and its
+// property records at records[word_off[q] ..).  Per chunk a visited lane writes its own record at
+// the rows done plus its rank in the ballot, and copies its property record (<= 17 words, a
+// per-lane loop, as k_props_gather) to the words done plus an exclusive scan of the chunk's word
+// counts.  The texts are copied as k_text_gather<false> copies clipped ones: the chunk's
+// destination offsets (a wave scan) and sources in LDS, the chunk's output units dealt across the
+// lanes in 4-byte destination words, the odd head, the tail and the carry between chunks stored
+// as single units.  (The dealing is written again here and not shared with k_text_gather: there
+// the clip, the marker unit and the per-segment A/B variant are woven into it, and a shared
+// helper would recompile a kernel whose timing is recorded.)  Rows, units and words are checked
+// against the query's three slots: the state cannot change between the passes, but a wrong count
+// must not become a store outside the result.
+__global__ void __launch_bounds__(MT_WAVE) k_walk_gather(DevState st, int nq, const uint32_t *docs,
+                                                         const int32_t *start, const int32_t *end, uint32_t what,
+                                                         int skip, const int32_t *end_seen, const int64_t *row_off,
+                                                         const int64_t *text_off, const int64_t *word_off,
+                                                         mt_walk_row *rows_out, uint16_t *text_out,
+                                                         uint32_t *records) {
+    __shared__ int s_dst[MT_WAVE], s_src[MT_WAVE];
+    const int q = blockIdx.x;
+    if (q >= nq) return;
+    WalkQuery Q = walk_query(st, q, docs, start, end);
+    const int64_t room_r = row_off[q + 1] - row_off[q], room_t = text_off[q + 1] - text_off[q],
+                  room_w = word_off[q + 1] - word_off[q];
+    if (Q.e <= 0 || room_r <= 0) return;
+    const int E = end_seen[q];   // the leaf action's end: an undefined one resolved by the count pass
+    const DocHdr h = st.hdr[Q.doc];
+    const SegRanges R = seg_ranges(st, Q.doc, h);
+    const PagedBase ar = doc_paged(st, Q.doc);   // (the arenas of the document's region)
+    const uint32_t P = (uint32_t)ar.P, T = (uint32_t)ar.T;
+    const uint32_t *pr = ar.props + (size_t)h.props_half * P * MT_PREC;
+    const uint16_t *tb = ar.text + (size_t)h.text_half * ar.T;
+    mt_walk_row *rw = rows_out + row_off[q];
+    uint32_t *rec = records + word_off[q];
+    uint16_t *o = text_out + text_off[q];
+    const int odd = (int)(((uintptr_t)o >> 1) & 1);   // the slot starts on the second half of a word
+    // unit u of the chunk (units of row sg start at s_dst[sg])
+    auto unit_at = [&](int u) -> uint32_t {
+        int sg = 0;
+#pragma unroll
+        for (int step = MT_WAVE / 2; step > 0; step >>= 1)
+            if (s_dst[sg + step] <= u) sg += step;
+        const uint32_t ix = (uint32_t)s_src[sg] + (uint32_t)(u - s_dst[sg]);
+        return ix < T ? tb[ix] : 0u;
+    };
+    int r0, pos, rows;
+    walk_seek(R, Q.s, skip, r0, pos, rows);
+    int64_t rows_done = 0, words_done = 0;
+    int64_t done = 0;        // units of the query produced so far (the carried one included)
+    bool carry = false;      // unit done - 1 is the first half of a word not yet stored
+    uint32_t carry_v = 0;
+    for (int r = r0; r < R.count() && pos < Q.e; r++) {
+        const v4i *A;
+        const v4u *Bv;
+        int n;
+        R.get(r, A, Bv, n);
+        for (int base = 0; base < n && pos < Q.e; base += MT_WAVE) {
+            const WalkLane L = walk_chunk(A, Bv, base + lane(), n, Q, what, pr, P, pos);
+            const u64 vm = ballot(L.vis);
+            if (!vm) continue;
+            const int incl = wave_scan_incl(L.units), winc = wave_scan_incl(L.wc);
+            const int64_t rank = rows_done + __popcll(vm & ((1ull << lane()) - 1ull));
+            const int64_t w0 = words_done + winc - L.wc, t0 = done + incl - L.units;
+            const bool wfits = (L.wc > 0) & (w0 + L.wc <= room_w);
+            const bool tfits = (L.units > 0) & (t0 + L.units <= room_t);
+            if (L.vis && rank < room_r) {
+                const bool marker = (L.b.z & MT_MARKER_BIT) != 0u;
+                mt_walk_row w;
+                w.row = rows + base + lane();
+                w.uid = L.b.z & ~MT_MARKER_BIT;
+                w.position = L.p0;
+                w.length = L.a.x;
+                w.seq = L.a.y >= MT_LOCAL_BASE ? -1 : L.a.y;
+                w.client = (int)(short)(L.a.w & 0xFFFF);
+                w.marker_ref_type = marker ? (int32_t)L.b.x : -1;
+                w.text = tfits ? (uint32_t)t0 : MT_PROPS_NONE;
+                w.props = wfits ? (uint32_t)w0 : MT_PROPS_NONE;
+                w.start = Q.s - L.p0;
+                w.end = E - L.p0;
+                w.flags = 0u;
+                rw[rank] = w;
+            }
+            if (wfits) {
+                const uint32_t *x = pr + (size_t)L.b.y * MT_PREC;   // (wc > 0: the handle is inside the arena)
+                rec[w0] = (uint32_t)(L.wc >> 1);
+                for (int k = 1; k < L.wc; k++) rec[w0 + k] = x[k];
+            }
+            rows_done += __popcll(vm);
+            words_done += bcast(winc, 63);
+            int tot = bcast(incl, 63);
+            // (the unit guard is apart from tfits on purpose: were a count ever wrong, a row cut by
+            // the room would have units stored and a text field of "nothing" -- never a stray store)
+            if (done + tot > room_t) tot = (int)(room_t - done);
+            if (tot <= 0) continue;
+            __syncthreads();   // the previous chunk's readers are done with the LDS arrays
+            s_dst[lane()] = incl - L.units;
+            s_src[lane()] = (int)L.b.x;
+            __syncthreads();
+            // chunk-local unit u lies at o[done + u]; u = -1 is the carried unit
+            int u0 = carry ? -1 : 0;
+            if (!carry && ((done + odd) & 1)) {   // the query's odd head (done == 0 here)
+                if (lane() == 0) o[done] = (uint16_t)unit_at(0);
+                u0 = 1;
+            }
+            const int npair = (tot - u0) >> 1;
+            for (int k = lane(); k < npair; k += MT_WAVE) {
+                const int u = u0 + 2 * k;
+                const uint32_t a = u < 0 ? carry_v : unit_at(u), b = unit_at(u + 1);
+                *(uint32_t *)(o + done + u) = a | (b << 16);
+            }
+            carry = ((tot - u0) & 1) != 0;
+            if (carry) carry_v = unit_at(tot - 1);
+            done += tot;
+        }
+        rows += n;
+    }
+    if (carry && lane() == 0) o[done - 1] = (uint16_t)carry_v;   // the tail
+}
+
 // ---------------------------------------------------------------- bulk delta-log read-out
 // mt_get_delta_log for many (doc, from_word) queries, and the rows of mt_delta_range: one wave
 // per query.  A query's span is its document's log from from_word to the word count (clamped
@@ -1498,7 +1751,8 @@ __global__ void __launch_bounds__(MT_WAVE) k_regen(DevState st, int doc, mt_rege
 
 // Device time of a bulk read-out's kernels: up to two brackets of HIP events, created on first
 // use; `timed` counts the brackets of the last read-out whose kernels have finished
-// (read_timer: mt_last_text_ms, mt_last_props_ms, mt_last_locate, mt_last_dlog_ms, mt_last_tiles).
+// (read_timer: mt_last_text_ms, mt_last_props_ms, mt_last_locate, mt_last_dlog_ms, mt_last_tiles,
+// mt_last_walk_ms).
 struct ReadTimer {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     int timed = 0;
@@ -1528,7 +1782,7 @@ struct mt_handle {
     bool load_timed = false;   // ev_load / ev_load1 bracket the last snapshot load's kernels
     // mt_get_texts, mt_get_prop_runs_bulk: around the counting pass, around the gather; the bulk
     // segment read-outs: around their kernel
-    ReadTimer tm_txt, tm_prp, tm_loc, tm_dlg, tm_tile;
+    ReadTimer tm_txt, tm_prp, tm_loc, tm_dlg, tm_tile, tm_walk;
     uint32_t *d_rst = nullptr;   // mt_delta_log_reset_docs: the listed documents (rst_cap of them)
     uint32_t rst_cap = 0;
     int64_t loc_n = 0, loc_host = 0;   // queries of the last segment read-out, of them answered by the host path
@@ -2108,7 +2362,7 @@ void mt_destroy(mt_handle *h) {
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->ev_load) hipEventDestroy(h->ev_load);
     if (h->ev_load1) hipEventDestroy(h->ev_load1);
-    for (ReadTimer *t : {&h->tm_txt, &h->tm_prp, &h->tm_loc, &h->tm_dlg, &h->tm_tile}) t->destroy();
+    for (ReadTimer *t : {&h->tm_txt, &h->tm_prp, &h->tm_loc, &h->tm_dlg, &h->tm_tile, &h->tm_walk}) t->destroy();
     if (h->d_rst) hipFree(h->d_rst);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -3785,6 +4039,105 @@ int mt_get_prop_runs_bulk_device(mt_handle *h, uint32_t n, const uint32_t *docs,
 int mt_last_props_ms(mt_handle *h, float *out) {
     if (!h || !out) return MT_E_INVALID;
     return read_timer(h, h->tm_prp, out);
+}
+
+// mt_walk_segments / mt_walk_segments_device: get_prop_runs_bulk's shape with three counts per
+// query (rows, text units, record words), so three prefix sums and three outputs; the count
+// pass also leaves every query's end as the leaf action sees it for the gather.
+static int walk_segments(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
+                         uint32_t what, int64_t *row_off, int64_t *text_off, int64_t *word_off, void *rows,
+                         uint64_t cap_rows, void *text, uint64_t cap_text, void *records, uint64_t cap_words,
+                         bool device) {
+    if (!h || !row_off || !text_off || !word_off) return MT_E_INVALID;
+    if (what & ~(MT_WALK_TEXT | MT_WALK_PROPS)) {
+        h->err = "mt_walk_segments: undefined bits in what (" + std::to_string(what) + ")";
+        return MT_E_INVALID;
+    }
+    int rc = check_queries(h, "mt_walk_segments", n, docs);
+    if (rc) return rc;
+    for (uint32_t q = 0; start && q < n; q++)
+        if (start[q] < 0) {
+            h->err = "mt_walk_segments: query " + std::to_string(q) + ": start below 0";
+            return MT_E_INVALID;
+        }
+    HIPCHK(h, hipSetDevice(h->device));
+    SETTLE(h);
+    ReadTimer &tm = h->tm_walk;
+    tm.timed = 0;
+    if (n == 0) return empty_offsets(h, {row_off, text_off, word_off}, device);
+    // extra: the three counts [n] each, the three offset arrays [n + 1] each, the ends [n]
+    const size_t cnt_w = (size_t)n * 3, off_w = ((size_t)n + 1) * 3, end_b = ((size_t)n * 4 + 7) & ~(size_t)7;
+    QueryCols qc;
+    HIPCHK(h, qc.upload(n, {docs, start, end}, (cnt_w + off_w) * 8 + end_b));
+    const uint32_t *d_docs = (const uint32_t *)qc.col[0];
+    const int32_t *d_start = (const int32_t *)qc.col[1], *d_end = (const int32_t *)qc.col[2];
+    int64_t *base = (int64_t *)qc.extra;
+    int64_t *d_cnt[3] = {base, base + n, base + 2 * (size_t)n};   // rows, units, words
+    int64_t *off[3] = {row_off, text_off, word_off};
+    int64_t *d_off[3];
+    for (int i = 0; i < 3; i++) d_off[i] = device ? off[i] : base + cnt_w + (size_t)i * (n + 1);
+    int32_t *d_ends = (int32_t *)(base + cnt_w + off_w);
+    // MT_LOCATE_ROW_WALK=1: walk from row 0 (the A/B of tools/walk_probe.py)
+    const char *rw = getenv("MT_LOCATE_ROW_WALK");
+    const int skip = !(rw && rw[0] == '1');
+    HIPCHK(h, tm.begin(0, h->stream));
+    hipLaunchKernelGGL(k_walk_count, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start, d_end, what,
+                       skip, d_cnt[0], d_cnt[1], d_cnt[2], d_ends);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, tm.end(0, h->stream));
+    int64_t total[3] = {0, 0, 0};
+    if ((rc = scan_counts(h, n, 3, d_cnt, off, device, total))) return rc;
+    tm.timed = 1;
+    if (!text) cap_text = 0;
+    if (!records) cap_words = 0;
+    const bool fits = cap_rows >= (uint64_t)total[0] && cap_text >= (uint64_t)total[1] && cap_words >= (uint64_t)total[2];
+    rc = after_counts(h, !rows, fits, total[0] == 0, [&] {
+        return "mt_walk_segments: the outputs hold " + std::to_string(cap_rows) + " rows, " + std::to_string(cap_text) +
+               " text units and " + std::to_string(cap_words) + " words, the results need " + std::to_string(total[0]) +
+               " rows, " + std::to_string(total[1]) + " text units and " + std::to_string(total[2]) + " words";
+    });
+    if (rc != RO_GATHER) return rc;
+    if (!device)
+        for (int i = 0; i < 3; i++)
+            HIPCHK(h, hipMemcpy(d_off[i], off[i], ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+    OutStage<mt_walk_row> g_rows;
+    OutStage<uint16_t> g_text;
+    OutStage<uint32_t> g_recs;
+    HIPCHK(h, g_rows.open(rows, device, (size_t)total[0]));
+    HIPCHK(h, g_text.open(text, device, (size_t)total[1]));
+    HIPCHK(h, g_recs.open(records, device, (size_t)total[2]));
+    HIPCHK(h, tm.begin(1, h->stream));
+    hipLaunchKernelGGL(k_walk_gather, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start, d_end, what,
+                       skip, (const int32_t *)d_ends, (const int64_t *)d_off[0], (const int64_t *)d_off[1],
+                       (const int64_t *)d_off[2], g_rows.p, g_text.p, g_recs.p);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, tm.end(1, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    tm.timed = 2;
+    HIPCHK(h, g_rows.copy_out(rows, (size_t)total[0]));
+    HIPCHK(h, g_text.copy_out(text, (size_t)total[1]));
+    HIPCHK(h, g_recs.copy_out(records, (size_t)total[2]));
+    return 0;
+}
+
+int mt_walk_segments(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
+                     uint32_t what, int64_t *row_off, int64_t *text_off, int64_t *word_off, mt_walk_row *rows,
+                     uint64_t cap_rows, uint16_t *text, uint64_t cap_text, uint32_t *records, uint64_t cap_words) {
+    return walk_segments(h, n, docs, start, end, what, row_off, text_off, word_off, rows, cap_rows, text, cap_text,
+                         records, cap_words, false);
+}
+
+int mt_walk_segments_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
+                            uint32_t what, void *row_off_dev, void *text_off_dev, void *word_off_dev, void *rows_dev,
+                            uint64_t cap_rows, void *text_dev, uint64_t cap_text, void *records_dev,
+                            uint64_t cap_words) {
+    return walk_segments(h, n, docs, start, end, what, (int64_t *)row_off_dev, (int64_t *)text_off_dev,
+                         (int64_t *)word_off_dev, rows_dev, cap_rows, text_dev, cap_text, records_dev, cap_words, true);
+}
+
+int mt_last_walk_ms(mt_handle *h, float *out) {
+    if (!h || !out) return MT_E_INVALID;
+    return read_timer(h, h->tm_walk, out);
 }
 
 int mt_get_prop_runs(mt_handle *h, uint32_t doc, uint32_t *runs, uint32_t cap_runs,

@@ -75,6 +75,13 @@ function jsCombine(op, cur, seq) {
     return cur;
 }
 
+// A referenceTileLabels value carries `label` when iterating it yields the label: an array that
+// holds it, or a string that holds it as one character (any other value carries none).
+function valueYieldsLabel(v, label) {
+    return (Array.isArray(v) && v.includes(label)) ||
+        (typeof v === "string" && label.length === 1 && v.includes(label));
+}
+
 class Interner {
     constructor() {
         this.keys = [];
@@ -138,10 +145,7 @@ class Interner {
         if (e === undefined) { e = { seen: 0, ids: [] }; this.labelSets.set(label, e); }
         for (; e.seen < this.vals.length; e.seen++) {
             const v = this.vals[e.seen];
-            if ((Array.isArray(v) && v.includes(label)) ||
-                (typeof v === "string" && label.length === 1 && v.includes(label))) {
-                e.ids.push(e.seen);
-            }
+            if (valueYieldsLabel(v, label)) { e.ids.push(e.seen); }
         }
         return e.ids;
     }
@@ -373,6 +377,7 @@ class BatchEncoder {
 }
 
 module.exports = {
+    valueYieldsLabel,
     BatchEncoder, Interner, Grow, canonical,
     OP_INSERT, OP_REMOVE, OP_ANNOTATE, OP_NOOP, F_GROUP_MORE, F_MARKER, F_LOCAL, F_ACK, NO_PROPS, VAL_NULL, VAL_UNDEF,
     VAL_FALSY_BIT, VAL_NOMATCH_BIT, jsCombine,

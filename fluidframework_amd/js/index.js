@@ -23,7 +23,7 @@
  */
 const assert = require("assert");
 const path = require("path");
-const { BatchEncoder, Interner, VAL_NULL } = require("./encode");
+const { BatchEncoder, Interner, VAL_NULL, valueYieldsLabel } = require("./encode");
 const { treeChunks, recordSpecs, emitTree } = require("./snapshot");
 
 // segment object -> its device id (mt_seg_info.uid) for getPosition outside a callback
@@ -470,6 +470,53 @@ class GpuMergeTreeBatch {
         return queries.map((_, q) => this._hit(w, 12 * q));
     }
 
+    /**
+     * Client.walkSegments for many ranges in one counting pass and one gather (mt_walk_segments),
+     * in the replica's own view.  queries: [{doc, start, end}] (start undefined: 0, end undefined:
+     * the document's length).  Per query the visited rows in document order as [{segment, pos,
+     * start, end}]: a row at position pos of length len is visited when len > 0, pos < end and
+     * pos + len > start (nothing is clamped; start == end strictly inside a segment visits it).
+     * `segment` is the document's object for that segment -- cachedLength, seq, clientId, text or
+     * refType, properties -- the one the delta events and getContainingSegment hand out; start
+     * and end are the leaf action's arguments (the query's minus pos, not clipped to the segment).
+     */
+    walkSegments(queries) {
+        this.flush();
+        const nil = (v) => v === undefined || v === null;
+        // (the device takes start >= 0, and an end below 0 for "the length": a start below 0
+        // visits what 0 visits, an end below 1 nothing)
+        const r = native.walkSegments(this.h, Uint32Array.from(queries, (q) => q.doc),
+            Int32Array.from(queries, (q) => (nil(q.start) ? 0 : Math.max(q.start, 0))),
+            Int32Array.from(queries, (q) => (nil(q.end) ? -1 : Math.max(q.end, 0))), 3);
+        const w = r.rows;
+        return queries.map((query, q) => {
+            const view = this.client(query.doc);
+            const rows = [];
+            for (let i = r.rowOff[q]; i < r.rowOff[q + 1]; i++) {
+                const o = 12 * i;
+                const st = { cachedLength: w[o + 3], seq: w[o + 4], clientId: w[o + 5] };
+                if (w[o + 6] >= 0) {
+                    st.type = "Marker";
+                    st.refType = w[o + 6];
+                } else {
+                    const at = r.textOff[q] + (w[o + 7] >>> 0);
+                    let text = "";
+                    for (let u = 0; u < st.cachedLength; u += 2048) {
+                        text += String.fromCharCode(...r.text.subarray(at + u, at + Math.min(st.cachedLength, u + 2048)));
+                    }
+                    st.type = "TextSegment";
+                    st.text = text;
+                }
+                const props = this._recordProps(r.records, r.wordOff[q], w[o + 8] >>> 0);
+                if (props !== undefined) { st.properties = props; }
+                const pos = w[o + 2];
+                rows.push({ segment: view._segObject(w[o + 1] >>> 0, st), pos,
+                    start: (nil(query.start) ? 0 : query.start) - pos, end: nil(query.end) ? w[o + 10] : query.end - pos });
+            }
+            return rows;
+        });
+    }
+
     _recordProps(records, base, rec) {
         if (rec === 0xFFFFFFFF) { return undefined; }
         const at = base + rec, n = records[at];
@@ -696,6 +743,73 @@ class GpuClient {
                 return this._textRange(start, end, placeholder.length ? placeholder.charCodeAt(0) : 0);
             },
         };
+    }
+
+    /**
+     * SharedString.getTextAndMarkers(label) (sharedString.ts:218): {parallelText, parallelMarkers}
+     * -- the document cut at every Tile marker whose referenceTileLabels carry the label: the
+     * markers, and before each of them the text since the previous one.  Built on the host from
+     * one whole-document walk, with the formatting the reference puts into these texts (DESIGN
+     * section 25): a text segment is bold when its font-weight property is truthy and underlined
+     * when its text-decoration is; ahead of its text come the closing tags of the styles that
+     * were open and no longer apply, in the order they were opened, then <b> / <u> for the ones
+     * that start.  Open styles carry across markers; two styles that start on one segment are
+     * kept as opened u-then-b, so a later segment that ends both closes </u></b>.  Markers
+     * without the label add nothing, and what follows the last labelled marker is not returned.
+     */
+    getTextAndMarkers(label) {
+        const STYLES = [["b", "font-weight"], ["u", "text-decoration"]];
+        const out = { parallelText: [], parallelMarkers: [] };
+        let open = [];      // the style tags open at this point of the document, oldest first
+        let piece = "";     // the text since the last labelled marker
+        this.walkSegments((segment) => {
+            const p = segment.properties;
+            if (segment.type === "Marker") {
+                if ((segment.refType & 1) && p && valueYieldsLabel(p.referenceTileLabels, label)) {
+                    out.parallelMarkers.push(segment);
+                    out.parallelText.push(piece);
+                    piece = "";
+                }
+                return true;
+            }
+            const wanted = STYLES.filter(([, key]) => p && p[key]).map(([tag]) => tag);
+            const ending = open.filter((tag) => !wanted.includes(tag));
+            const starting = wanted.filter((tag) => !open.includes(tag));
+            open = open.filter((tag) => wanted.includes(tag)).concat(starting.slice().reverse());
+            piece += ending.map((tag) => `</${tag}>`).join("") + starting.map((tag) => `<${tag}>`).join("") + segment.text;
+            return true;
+        });
+        return out;
+    }
+
+    /**
+     * Client.walkSegments(handler, start?, end?, accum?, splitRange = false) (client.ts:276-285 ->
+     * MergeTree.mapRange / nodeMap, mergeTree.ts:2830-2840, :2936-2998; SharedSegmentSequence.
+     * walkSegments, sequence.ts:372): handler(segment, pos, refSeq, clientId, start, end, accum)
+     * for every visible segment that intersects the range, in document order, until the handler
+     * returns a falsy value (nodeMap's `if (!go) break`).  The read-out is one call on the device
+     * (GpuMergeTreeBatch.walkSegments); the early exit happens here.  splitRange is not offered:
+     * it splits segments of the replica.
+     */
+    walkSegments(handler, start, end, accum, splitRange = false) {
+        if (splitRange) {
+            throw new Error("merge-tree replay: walkSegments with splitRange is not offered (it changes the replica)");
+        }
+        this._sync();
+        for (const r of this.batch.walkSegments([{ doc: this.doc, start, end }])[0]) {
+            if (!handler(r.segment, r.pos, this.getCurrentSeq(), this.getClientId(), r.start, r.end, accum)) { break; }
+        }
+    }
+
+    /**
+     * Client.getRangeExtentsOfPosition(pos) (client.ts:1026-1043): the first position of the
+     * segment holding pos and the position after it; both undefined when there is no segment.
+     */
+    getRangeExtentsOfPosition(pos) {
+        this._sync();
+        const hit = this.batch.getContainingSegments([{ doc: this.doc, pos }])[0];
+        if (hit === undefined) { return { posStart: undefined, posAfterEnd: undefined }; }
+        return { posStart: hit.position, posAfterEnd: hit.position + hit.length };
     }
 
     /** Client.getPropertiesAtPosition (client.ts:1011-1025): one width-1 query on the device. */

@@ -537,6 +537,60 @@ int mt_find_markers_by_id_device(mt_handle *h, uint32_t n, const uint32_t *docs,
    0 instead of finding H's page by the directory and moving away from it page by page (the A/B
    of tools/tile_probe.py; results are identical). */
 int mt_last_tiles(mt_handle *h, int64_t *out /* [2] */, float *ms);
+/* ---- bulk ranged segment walk: SharedSegmentSequence.walkSegments(handler, start, end)
+        (SEQ/sequence.ts:372 -> Client.walkSegments, MT/client.ts:276-285 -> MergeTree.mapRange /
+        nodeMap, MT/mergeTree.ts:2830-2840, :2936-2998) for n (doc, start, end) queries in one
+        counting pass and one gather on the device; the view is the replica's own, as in
+        mt_get_texts (on a live handle the local client's unacked inserts are in, its pending
+        removes out).  With pos a row's observer position and len its observer length, the row
+        is visited iff len > 0, pos < end and pos + len > start (nodeMap's test on the shifted
+        start / end); rows come in document order and nothing is clamped: start == end strictly
+        inside a segment visits that segment, on a boundary nothing; start > end visits a row
+        only when it spans both; start >= length visits nothing; end > length behaves as length.
+        splitRange is not offered (it changes the replica).
+        Arguments and errors are mt_get_prop_runs_bulk's: docs NULL: documents 0..n-1; start
+        NULL: 0; end NULL or end[q] < 0: the document's length; start[q] < 0, a doc >= n_docs
+        or an undefined bit of `what` is MT_E_INVALID, checked before anything is launched (the
+        message names the query); documents may repeat in any order; failed documents answer
+        from where they stopped; n == 0 is fine.  rows NULL is a sizing-only call; any capacity
+        too small returns MT_E_OVERFLOW with nothing written (the message names the three
+        needs); the three offset arrays (n + 1 each) are always written.
+        Query q's records are rows[row_off[q] .. row_off[q + 1]).  A visited text row
+        contributes its whole text (length units at text[text_off[q] + row.text]), not the part
+        inside the range: the handler receives the segment and takes substring(start, end)
+        itself, as gatherText does.  Without MT_WALK_TEXT / MT_WALK_PROPS the matching counts
+        are 0 and the fields read 0xFFFFFFFF. ---- */
+#define MT_WALK_TEXT 1u
+#define MT_WALK_PROPS 2u
+typedef struct mt_walk_row {     /* 48 bytes */
+    int32_t row;                 /* index in document order */
+    uint32_t uid;
+    int32_t position;            /* the walk's pos: observer lengths before the row */
+    int32_t length;              /* cachedLength */
+    int32_t seq, client;         /* -1: unassigned (live handles) */
+    int32_t marker_ref_type;     /* -1: a TextSegment */
+    uint32_t text;               /* first unit of the row's whole text, relative to text_off[q];
+                                    0xFFFFFFFF: a marker, or text not asked for */
+    uint32_t props;              /* offset of [count, (key, value) x count] relative to word_off[q];
+                                    0xFFFFFFFF: properties undefined, or not asked for ({} is a
+                                    record of count 0) */
+    int32_t start, end;          /* the leaf action's arguments: start[q] - position, end - position
+                                    (not clipped to the segment) */
+    uint32_t flags;              /* 0 */
+} mt_walk_row;
+int mt_walk_segments(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
+                     uint32_t what, int64_t *row_off, int64_t *text_off, int64_t *word_off, mt_walk_row *rows,
+                     uint64_t cap_rows, uint16_t *text, uint64_t cap_text, uint32_t *records, uint64_t cap_words);
+/* The same with the three offset arrays and the three outputs in device memory on the handle's
+   device; the query arrays stay host arrays. */
+int mt_walk_segments_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
+                            uint32_t what, void *row_off_dev, void *text_off_dev, void *word_off_dev, void *rows_dev,
+                            uint64_t cap_rows, void *text_dev, uint64_t cap_text, void *records_dev,
+                            uint64_t cap_words);
+/* Device time (ms, HIP events) of the last walk's counting pass and gather.  MT_LOCATE_ROW_WALK=1
+   makes the walk start at row 0 instead of at the page the directory names for start (the A/B
+   of tools/walk_probe.py; results are identical). */
+int mt_last_walk_ms(mt_handle *h, float *out /* [2] */);
 /* Debug: raw segment records (8 u32 per segment: segA then segB) and the 32-word header. */
 int mt_debug_raw(mt_handle *h, uint32_t doc, uint32_t *rows, uint32_t cap_rows, uint32_t *n_rows,
                  int32_t *hdr_words);

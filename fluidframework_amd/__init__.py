@@ -23,6 +23,13 @@ class DeltaLogOverflow(RuntimeError):
         self.records = records
 
 
+def props_signature(pairs):
+    """The device's 12-bit signature of a property set (mt_props_signature): pairs is a sequence
+    of (key id, value id).  Needs the library, not a GPU."""
+    a = np.ascontiguousarray(np.asarray(list(pairs), dtype=np.uint32).reshape(-1, 2))
+    return int(_native.load().mt_props_signature(_native.ptr(a), a.shape[0]))
+
+
 class PinnedArray:
     """A page-locked host buffer (mt_host_alloc) and its numpy view (`a`); the buffer is freed
     with this object, so keep it alive while the view is in use."""
@@ -1050,6 +1057,15 @@ class MergeTreeBatch:
         self._check(self.lib.mt_debug_raw(self.h, doc, _native.ptr(rows), n.value, ctypes.byref(n), None),
                     "mt_debug_raw")
         return rows[:n.value], hdr
+
+    def debug_props_sigs(self, doc):
+        """The property-set signature each segment row carries (mt_debug_props_sigs)."""
+        n = ctypes.c_uint32()
+        self._check(self.lib.mt_debug_props_sigs(self.h, doc, None, 0, ctypes.byref(n)), "mt_debug_props_sigs")
+        sigs = np.zeros(max(n.value, 1), dtype=np.uint32)
+        self._check(self.lib.mt_debug_props_sigs(self.h, doc, _native.ptr(sigs), n.value, ctypes.byref(n)),
+                    "mt_debug_props_sigs")
+        return sigs[:n.value]
 
     def is_paged(self, doc):
         """True when the document lives in the paged layout (DESIGN.md 'Paged documents')."""

@@ -154,6 +154,8 @@ SIGNATURES = [
     ("mt_delta_log_reset_docs", _I, [_P, _U32, _P]),
     ("mt_last_dlog_ms", _I, [_P, _P]),
     ("mt_debug_raw", _I, [_P, _U32, _P, _U32, _P, _P]),
+    ("mt_debug_props_sigs", _I, [_P, _U32, _P, _U32, _P]),
+    ("mt_props_signature", _U32, [_P, _I]),
     ("mt_debug_pick", _I, [_P, _P, _U32, _P]),
     ("mt_debug_prof", _I, [_P, _P, _I]),
     ("mt_maintenance_counts", _I, [_P, _P]),

@@ -164,6 +164,29 @@ template <class T> __device__ __forceinline__ void wsync() {
 #define SEGF_NONL 8u       // its text holds no '\n' at all: every piece a split makes ends
                            // without one (the trailing-'\n' flag is known without a text read)
 #define SEGF_SLACK_SHIFT 16 // bits 16..31: arena units reserved after the text for appends
+// bits 4..15: a 12-bit signature of the property set the row's handle names -- the sum modulo
+// 4096 of mt_psig_mix over the record's stored pairs (0 for handle 0).  A sum, so it does not
+// depend on the pairs' order and follows a replaced, deleted or appended pair from the stored
+// bits alone.  Wherever rows are at rest the bits equal the signature of the record b.y names;
+// two sets with different signatures differ, so zamboni's matchProperties answers most
+// comparisons without reading either record (match_props).  -DMT_NO_PSIG: the bits stay 0.
+#define SEGF_PSIG_SHIFT 4
+#define SEGF_PSIG_MASK 0xFFF0u
+__host__ __device__ inline uint32_t mt_psig_mix(uint32_t k, uint32_t v) {
+    uint32_t h = (k * 0x9E3779B1u + v) * 0x85EBCA6Bu;
+    h ^= h >> 15;
+    h *= 0xC2B2AE35u;
+    return (h >> 18) & 0xFFFu;
+}
+// a row's flags word with the signature bits replaced / the word's signature
+__host__ __device__ inline uint32_t psig_put(uint32_t w, uint32_t sig) {
+#ifdef MT_NO_PSIG
+    return w & ~SEGF_PSIG_MASK;
+#else
+    return (w & ~SEGF_PSIG_MASK) | ((sig << SEGF_PSIG_SHIFT) & SEGF_PSIG_MASK);
+#endif
+}
+__host__ __device__ inline uint32_t psig_of(uint32_t w) { return (w & SEGF_PSIG_MASK) >> SEGF_PSIG_SHIFT; }
 __device__ __forceinline__ int text_slack(int len) { return min((len >> 1) + 8, 4096); }
 
 __device__ static const uint32_t kEmptyPropsRec = 0u;
@@ -1276,11 +1299,16 @@ TD bool props_ensure(DocT<T> &d, int need) {
     return false;
 }
 // Properties.matchProperties MT/properties.ts:61-92 over interned ids; nm: either set holds a
-// NaN / undefined value (SEGF_NOMATCH), which no comparison finds equal
-TD bool match_props(DocT<T> &d, uint32_t ha, uint32_t hb, bool nm) {
+// NaN / undefined value (SEGF_NOMATCH), which no comparison finds equal; wa / wb: the two rows'
+// flags words -- sets whose signatures differ are different, and neither record is read (equal
+// signatures say nothing: the records decide)
+TD bool match_props(DocT<T> &d, uint32_t ha, uint32_t hb, bool nm, uint32_t wa, uint32_t wb) {
     if (ha == 0 || hb == 0) return ha == hb;
     if (nm) return false;
     if (ha == hb) return true;
+#ifndef MT_NO_PSIG
+    if ((wa ^ wb) & SEGF_PSIG_MASK) return false;
+#endif
     const GLB_AS uint32_t *a = prec(d, d.props_half, ha), *b = prec(d, d.props_half, hb);
     const uint32_t na = a[0], nbb = b[0];
     if (na != nbb) return false;
@@ -1707,7 +1735,7 @@ TD int scour_block(DocT<T> &d, int s, int e) {
     uint32_t owners = 0;
     int prev = -1, plen = 0;
     bool pmark = false, pnl = false, pnm = false;
-    uint32_t pprops = 0;
+    uint32_t pprops = 0, pw = 0;
     for (int j = 0; j < cntb; j++) {
         uint32_t own = (uint32_t)j;
         if ((m_unlink >> j) & 1ull) {
@@ -1719,9 +1747,10 @@ TD int scour_block(DocT<T> &d, int s, int e) {
             const int lj = bcast(a.x, j);
             const bool mk = (m_mark >> j) & 1ull, nl = (m_nl >> j) & 1ull;
             const uint32_t pj = (uint32_t)bcast((int)b.y, j);
-            const bool nmj = (bcast((int)b.w, j) & SEGF_NOMATCH) != 0;
+            const uint32_t wj = (uint32_t)bcast((int)b.w, j);
+            const bool nmj = (wj & SEGF_NOMATCH) != 0;
             const bool ok = prev >= 0 && lj > 0 && can_append(plen, pmark, pnl, lj, mk) &&
-                            match_props(d, pprops, pj, pnm || nmj);
+                            match_props(d, pprops, pj, pnm || nmj, pw, wj);
             if (ok) {
                 own = (uint32_t)prev;
                 plen += lj;
@@ -1732,6 +1761,7 @@ TD int scour_block(DocT<T> &d, int s, int e) {
                 pmark = mk;
                 pnl = !mk && lj > 0 && nl;
                 pprops = pj;
+                pw = wj;
                 pnm = nmj;
             }
         }
@@ -1837,7 +1867,9 @@ TD int scour_block(DocT<T> &d, int s, int e) {
                 d.A[s + kk].x = gk;
                 v4u nb = bk;
                 nb.x = newoff;
-                nb.w = (lastw & (SEGF_NL_KNOWN | SEGF_NL)) | nonl | (newslack << SEGF_SLACK_SHIFT);
+                // (the keeper's set stays: its own signature bits)
+                nb.w = (lastw & (SEGF_NL_KNOWN | SEGF_NL)) | nonl | (bk.w & SEGF_PSIG_MASK) |
+                       (newslack << SEGF_SLACK_SHIFT);
                 d.Bv[s + kk] = nb;
             }
             wsync<T>();
@@ -1908,6 +1940,11 @@ TD ScourPlan scour_plan(DocT<T> &d, const v4i &a, v4u &b, bool in, bool pend, in
     const u64 m_mark = ballot(in && marker);
     const u64 m_nl = ballot(in && (b.w & SEGF_NL) != 0);
     const uint32_t pprops = (uint32_t)__shfl_up((int)b.y, 1, MT_WAVE);
+#ifdef MT_NO_PSIG
+    const uint32_t pw = 0;
+#else
+    const uint32_t pw = (uint32_t)__shfl_up((int)b.w, 1, MT_WAVE);   // (its signature bits)
+#endif
     const bool pc = k > 0 && ((m_cand >> (k - 1)) & 1ull);
     const bool pm = k > 0 && ((m_mark >> (k - 1)) & 1ull);
     const bool pn = k > 0 && ((m_nl >> (k - 1)) & 1ull);
@@ -1918,7 +1955,7 @@ TD ScourPlan scour_plan(DocT<T> &d, const v4i &a, v4u &b, bool in, bool pend, in
 #endif
     const bool nm = ((m_nm >> k) & 1ull) || (k > 0 && ((m_nm >> (k - 1)) & 1ull));
     bool join = cand && pc && k != start && !marker && !pm && !pn && a.x > 0;
-    if (join && (nm || pprops != b.y)) join = match_props(d, pprops, b.y, nm);
+    if (join && (nm || pprops != b.y)) join = match_props(d, pprops, b.y, nm, pw, b.w);
     ScourPlan p;
     p.m_join = ballot(join);
     p.big = ballot(join && a.x > MT_GRAN) != 0;
@@ -2020,7 +2057,9 @@ TD ScourKeeper scour_group(DocT<T> &d, const v4u &bk, int ak, const v4u &bm, int
             if (t < gk) tb[(move_keeper ? (int)newoff : dst - ak) + t] = ch;
         }
     }
-    return ScourKeeper{gk, newoff, (lastw & (SEGF_NL_KNOWN | SEGF_NL)) | nonl | (newslack << SEGF_SLACK_SHIFT)};
+    return ScourKeeper{gk, newoff,
+                       (lastw & (SEGF_NL_KNOWN | SEGF_NL)) | nonl | (bk.w & SEGF_PSIG_MASK) |
+                           (newslack << SEGF_SLACK_SHIFT)};
 }
 // The merges of a plan on rows in registers (the paged in-place routes, mt_paged.h); the room
 // for g.totc units is the caller's to ensure.  The keepers' lanes (g.m_grp) leave with their
@@ -2486,7 +2525,7 @@ TD void op_insert(DocT<T> &d, const OpIn &in, const GLB_AS uint16_t *tin, const 
         fail_cap(d, 1);
         return;
     }
-    uint32_t ph = 0, nomatch = 0;
+    uint32_t ph = 0, nomatch = 0;   // nomatch: the set's bits of the flags word (SEGF_NOMATCH, signature)
     if (op.props != MT_NO_PROPS) {
         ph = (uint32_t)d.props_top;
         d.props_top++;
@@ -2516,6 +2555,14 @@ TD void op_insert(DocT<T> &d, const OpIn &in, const GLB_AS uint16_t *tin, const 
             nm = nm || (v != MT_VAL_NULL && (v & MT_VAL_NOMATCH_BIT));
         }
         if (nm) nomatch = SEGF_NOMATCH;
+#endif
+#ifndef MT_NO_PSIG
+        uint32_t sig = 0;   // of the pairs stored above
+        for (uint32_t j = 0; j < cntk; j++) {
+            const uint32_t v = rec[2 + 2 * j];
+            if (v != MT_VAL_NULL) sig += mt_psig_mix(rec[1 + 2 * j], v);
+        }
+        nomatch = psig_put(nomatch, sig);
 #endif
     }
     int bstart;
@@ -2673,13 +2720,19 @@ TD bool grp_pending_key(DocT<T> &d, const PendQ &pw, uint32_t k) {
 // the whole op (:48-51: *undef = true, propertyDeltas undefined, the set unchanged).
 TD bool annotate_record(DocT<T> &d, uint32_t oh, uint32_t nh, const GLB_AS uint32_t *rec, u64 &sh,
                         GLB_AS int32_t *logp, int &nlog, bool *nomatch = nullptr, PendQ pw = pq_zero(),
-                        bool *undef = nullptr) {
+                        bool *undef = nullptr, uint32_t *psig = nullptr) {
     const uint32_t cntk = rec[0] & 0xFFFF, comb = rec[0] >> 16;
     const GLB_AS uint32_t *o = oh ? prec(d, d.props_half, oh) : nullptr;
     GLB_AS uint32_t *t = prec(d, d.props_half, nh);
     const uint32_t on = o ? o[0] : 0;
     uint32_t n = 0;
     int npd = 0;
+    // psig in: the old set's signature; out: the new set's, moved by every pair that leaves,
+    // changes or joins the record below (modulo 4096: the caller masks)
+    uint32_t sg = 0;
+#ifndef MT_NO_PSIG
+    if (psig) sg = *psig;
+#endif
     if constexpr (T::kLive) {
         if (pq_any(pw) && grp_pending_rewrite(d, pw)) {
             for (uint32_t i = 0; i < 2 * on; i++) t[1 + i] = o[1 + i];
@@ -2718,6 +2771,9 @@ TD bool annotate_record(DocT<T> &d, uint32_t oh, uint32_t nh, const GLB_AS uint3
                 logp[nlog++] = (int32_t)dv;
             }
             npd++;
+#ifndef MT_NO_PSIG
+            sg -= mt_psig_mix(k, v);
+#endif
         } else {
             t[1 + 2 * n] = k;
             t[2 + 2 * n] = v;
@@ -2767,6 +2823,10 @@ TD bool annotate_record(DocT<T> &d, uint32_t oh, uint32_t nh, const GLB_AS uint3
             }
         }
 #endif
+#ifndef MT_NO_PSIG
+        if (idx >= 0) sg -= mt_psig_mix(k, t[2 + 2 * idx]);
+        if (nv != MT_VAL_NULL) sg += mt_psig_mix(k, nv);
+#endif
         if (nv == MT_VAL_NULL) {
             if (idx >= 0) {
                 for (uint32_t q = (uint32_t)idx + 1; q < n; q++) {
@@ -2785,6 +2845,9 @@ TD bool annotate_record(DocT<T> &d, uint32_t oh, uint32_t nh, const GLB_AS uint3
         }
     }
     t[0] = n;
+#ifndef MT_NO_PSIG
+    if (psig) *psig = sg;
+#endif
     sh = fnv_u32(sh, (uint32_t)npd);
     // *nomatch in: the new set can hold a NaN / undefined value at all; out: it does
     if (nomatch && *nomatch) {
@@ -2905,10 +2968,12 @@ TD bool range_mark(DocT<T> &d, const mt_op_rec &op, const GLB_AS uint32_t *rec, 
                     pw = pq;
                 }
             }
-            if (!annotate_record(d, bv.y, nh, rec, sh, (GLB_AS int32_t *)nullptr, unused, &nm, pw)) bad = true;
+            uint32_t sg = psig_of(bv.w);
+            if (!annotate_record(d, bv.y, nh, rec, sh, (GLB_AS int32_t *)nullptr, unused, &nm, pw, nullptr, &sg))
+                bad = true;
             v4u nb = bv;
             nb.y = nh;
-            nb.w = (bv.w & ~SEGF_NOMATCH) | (nm ? SEGF_NOMATCH : 0u);
+            nb.w = psig_put((bv.w & ~SEGF_NOMATCH) | (nm ? SEGF_NOMATCH : 0u), sg);
             d.Bv[i] = nb;
         }
         if (ballot(bad)) {

@@ -1678,7 +1678,7 @@ TD bool pg_pack_inplace(PagedDoc<T> &pd, int pg, v4i a, v4u b, const ScourPlan &
         const uint32_t lastw = (uint32_t)__shfl((int)b.w, g1.gend & (MT_WAVE - 1), MT_WAVE);
         if ((g1.m_grp >> k) & 1ull) {
             a1.x = g1.glen;
-            b1.w = lastw & (SEGF_NL_KNOWN | SEGF_NL);
+            b1.w = (lastw & (SEGF_NL_KNOWN | SEGF_NL)) | (b.w & SEGF_PSIG_MASK);   // (the keeper's set)
         }
     }
     const int d1 = k < bstart ? k

@@ -89,6 +89,7 @@ __global__ void __launch_bounds__(MT_WAVE) k_load_header(DevState st, const int6
             break;
         }
         bool bad = false, nm = false;
+        uint32_t sig = 0;   // of the stored pairs (SEGF_PSIG_MASK)
         if (hp) {   // TextSegment.make / Marker.make(props): keys with null dropped (Q5)
             const uint32_t *rec = pin + r.props;
             const uint32_t cnt = rec[0] & 0xFFFF;
@@ -103,6 +104,7 @@ __global__ void __launch_bounds__(MT_WAVE) k_load_header(DevState st, const int6
                 t[1 + 2 * k] = rec[1 + 2 * j];
                 t[2 + 2 * k] = rec[2 + 2 * j];
                 nm = nm || (rec[2 + 2 * j] & MT_VAL_NOMATCH_BIT) != 0;
+                sig += mt_psig_mix(rec[1 + 2 * j], rec[2 + 2 * j]);
                 k++;
             }
             t[0] = k;
@@ -123,6 +125,7 @@ __global__ void __launch_bounds__(MT_WAVE) k_load_header(DevState st, const int6
             uint32_t w = 0;
             if (tl > 0) w = SEGF_NL_KNOWN | (tin[r.payload + tl - 1] == '\n' ? SEGF_NL : 0u);
             if (nm) w |= SEGF_NOMATCH;
+            w = psig_put(w, sig);
             dA[i] = v4i{r.len, r.seq, r.removed_seq, pack_cli(r.client, rem ? r.removed_client : 0)};
             dO[i] = 0ull;
             if (st.segP && !big) {   // no pending groups
@@ -4837,10 +4840,28 @@ int mt_debug_raw(mt_handle *h, uint32_t doc, uint32_t *rows, uint32_t cap_rows, 
     for (int i = 0; i < n && rows && (uint32_t)i < cap_rows; i++) {
         memcpy(rows + 8 * i, &hd.A[i], 16);
         memcpy(rows + 8 * i + 4, &hd.B[i], 16);
+        rows[8 * i + 7] &= ~SEGF_PSIG_MASK;   // the signature bits stay on the device
     }
     if (n_rows) *n_rows = (uint32_t)n;
     if (hdr_words) memcpy(hdr_words, &hd.hdr, sizeof(DocHdr));
     return 0;
+}
+
+// Debug: the property-set signature each row carries (the bits no other read-out returns).
+int mt_debug_props_sigs(mt_handle *h, uint32_t doc, uint32_t *sigs, uint32_t cap_rows, uint32_t *n_rows) {
+    HostDoc hd;
+    int rc = fetch_doc(h, doc, hd, false, false);
+    if (rc) return rc;
+    const int n = hd.hdr.n_seg;
+    for (int i = 0; i < n && sigs && (uint32_t)i < cap_rows; i++) sigs[i] = psig_of(hd.B[i].w);
+    if (n_rows) *n_rows = (uint32_t)n;
+    return 0;
+}
+
+uint32_t mt_props_signature(const uint32_t *pairs, int n) {
+    uint32_t sig = 0;
+    for (int j = 0; j < n; j++) sig += mt_psig_mix(pairs[2 * j], pairs[2 * j + 1]);
+    return sig & 0xFFFu;
 }
 
 // Debug (flat documents): the zamboni heap in array order as {maxSeq, leaf index of its

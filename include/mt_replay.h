@@ -594,6 +594,15 @@ int mt_last_walk_ms(mt_handle *h, float *out /* [2] */);
 /* Debug: raw segment records (8 u32 per segment: segA then segB) and the 32-word header. */
 int mt_debug_raw(mt_handle *h, uint32_t doc, uint32_t *rows, uint32_t cap_rows, uint32_t *n_rows,
                  int32_t *hdr_words);
+/* The 12-bit signature of a property set the device keeps in each segment row (csrc/mt_engine.h
+   SEGF_PSIG_MASK): the sum modulo 4096 of one mix per stored {key, value} pair (pairs: n pairs
+   of interned ids), so it does not depend on the pairs' order; 0 for no pairs.  Sets with
+   different signatures differ; equal signatures decide nothing.  A library built with
+   -DMT_NO_PSIG keeps every row's bits at 0. */
+uint32_t mt_props_signature(const uint32_t *pairs, int n);
+/* Debug: the signature bits of each segment row of a document (n_rows rows, in order); no
+   other read-out returns them. */
+int mt_debug_props_sigs(mt_handle *h, uint32_t doc, uint32_t *sigs, uint32_t cap_rows, uint32_t *n_rows);
 /* Debug: which kernel variant (csrc/mt_variants.h) a described launch runs and the dynamic LDS
    bytes it is given -- the library's own choice, answered without a device.  launch names the
    launch site; the handle facts are delta_log (delta_log_capacity > 0), ordinals

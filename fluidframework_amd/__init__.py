@@ -878,43 +878,63 @@ class MergeTreeBatch:
         what = (_native.MT_WALK_TEXT if text else 0) | (_native.MT_WALK_PROPS if props else 0)
         return n, docs, start, end, what
 
-    def walk_segments(self, docs=None, start=None, end=None, text=True, props=True):
+    @staticmethod
+    def _view_cols(n, ref_seq, client):
+        """ref_seq / client as mt_walk_segments_view takes them: None stays NULL, scalars broadcast."""
+        return tuple(None if x is None else np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.int32), (n,)))
+                     for x in (ref_seq, client))
+
+    def walk_segments(self, docs=None, start=None, end=None, text=True, props=True, ref_seq=None, client=None):
         """(row_off, rows, text_off, text, word_off, records): query q's visited rows, in document
         order, are rows[row_off[q]:row_off[q + 1]] (WALK_ROW_DTYPE).  A row is visited when its
         observer length is > 0, its position is < end and its position + length is > start
         (nothing is clamped: start == end inside a segment visits it).  A text row's whole text
         is text[text_off[q] + row.text:][:row.length] (UTF-16 units), its property record
         [count, (key, value) x count] starts at records[word_off[q] + row.props]; either field
-        is 0xFFFFFFFF when there is none or it was not asked for.  Queries as in get_texts."""
+        is 0xFFFFFFFF when there is none or it was not asked for.  Queries as in get_texts.
+        ref_seq / client (one value, or one per query): MergeTree.mapRange's view -- lengths,
+        positions, start and end are then the (refSeq, client) view's (mt_walk_segments_view);
+        client 0 is the replica's own view; rows of a query answered on the host carry
+        MT_WALK_HOST in `flags`."""
         n, docs, start, end, what = self._walk_queries(docs, start, end, text, props)
         row_off, text_off, word_off = (np.zeros(n + 1, dtype=np.int64) for _ in range(3))
-        args = (self.h, n, _native.ptr(docs), _native.ptr(start), _native.ptr(end), what, _native.ptr(row_off),
-                _native.ptr(text_off), _native.ptr(word_off))
-        self._check(self.lib.mt_walk_segments(*args, None, 0, None, 0, None, 0), "mt_walk_segments")
+        fn, name, view = self.lib.mt_walk_segments, "mt_walk_segments", ()
+        if ref_seq is not None or client is not None:
+            fn, name = self.lib.mt_walk_segments_view, "mt_walk_segments_view"
+            cols = self._view_cols(n, ref_seq, client)   # (kept alive for the calls below)
+            view = tuple(_native.ptr(x) for x in cols)
+        args = (self.h, n, _native.ptr(docs), _native.ptr(start), _native.ptr(end)) + view + (
+            what, _native.ptr(row_off), _native.ptr(text_off), _native.ptr(word_off))
+        self._check(fn(*args, None, 0, None, 0, None, 0), name)
         nr, nt, nw = int(row_off[n]), int(text_off[n]), int(word_off[n])
         rows = np.zeros(max(nr, 1), dtype=_native.WALK_ROW_DTYPE)
         units = np.zeros(max(nt, 1), dtype=np.uint16)
         recs = np.zeros(max(nw, 1), dtype=np.uint32)
-        self._check(self.lib.mt_walk_segments(*args, _native.ptr(rows), nr, _native.ptr(units), nt, _native.ptr(recs), nw),
-                    "mt_walk_segments")
+        self._check(fn(*args, _native.ptr(rows), nr, _native.ptr(units), nt, _native.ptr(recs), nw), name)
         return row_off, rows[:nr], text_off, units[:nt], word_off, recs[:nw]
 
-    def walk_segments_device(self, docs=None, start=None, end=None, text=True, props=True, out=None):
+    def walk_segments_device(self, docs=None, start=None, end=None, text=True, props=True, out=None, ref_seq=None,
+                             client=None):
         """walk_segments with the results left on the handle's device: (row_off, rows, text_off,
         text, word_off, records) torch tensors (int64 [n + 1] offsets; rows int32 [R, 12] holding
         the records' words, text int16, records int32).  out: (rows, text, records) tensors of
         those types on that device to fill (at least the results' sizes); the results are then
         their leading slices.  (torch is imported before the first handle is created, as for
-        get_texts_device.)"""
+        get_texts_device.)  ref_seq / client as in walk_segments."""
         import torch
         n, docs, start, end, what = self._walk_queries(docs, start, end, text, props)
         dev = torch.device("cuda", self.device)
         row_off, text_off, word_off = (torch.empty(n + 1, dtype=torch.int64, device=dev) for _ in range(3))
-        args = (self.h, n, _native.ptr(docs), _native.ptr(start), _native.ptr(end), what,
-                ctypes.c_void_p(row_off.data_ptr()), ctypes.c_void_p(text_off.data_ptr()),
-                ctypes.c_void_p(word_off.data_ptr()))
+        fn, name, view = self.lib.mt_walk_segments_device, "mt_walk_segments_device", ()
+        if ref_seq is not None or client is not None:
+            fn, name = self.lib.mt_walk_segments_view_device, "mt_walk_segments_view_device"
+            cols = self._view_cols(n, ref_seq, client)   # (kept alive for the calls below)
+            view = tuple(_native.ptr(x) for x in cols)
+        args = (self.h, n, _native.ptr(docs), _native.ptr(start), _native.ptr(end)) + view + (
+            what, ctypes.c_void_p(row_off.data_ptr()), ctypes.c_void_p(text_off.data_ptr()),
+            ctypes.c_void_p(word_off.data_ptr()))
         if out is None:
-            self._check(self.lib.mt_walk_segments_device(*args, None, 0, None, 0, None, 0), "mt_walk_segments_device")
+            self._check(fn(*args, None, 0, None, 0, None, 0), name)
             rows = torch.empty((max(int(row_off[n]), 1), 12), dtype=torch.int32, device=dev)
             units = torch.empty(max(int(text_off[n]), 1), dtype=torch.int16, device=dev)
             recs = torch.empty(max(int(word_off[n]), 1), dtype=torch.int32, device=dev)
@@ -926,10 +946,8 @@ class MergeTreeBatch:
                                      "the handle's device")
             if rows.dim() != 2 or rows.shape[1] != 12 or units.dim() != 1 or recs.dim() != 1:
                 raise ValueError("walk_segments_device: out is (rows [R, 12], text [units], records [words])")
-        self._check(self.lib.mt_walk_segments_device(*args, ctypes.c_void_p(rows.data_ptr()), rows.shape[0],
-                                                     ctypes.c_void_p(units.data_ptr()), units.numel(),
-                                                     ctypes.c_void_p(recs.data_ptr()), recs.numel()),
-                    "mt_walk_segments_device")
+        self._check(fn(*args, ctypes.c_void_p(rows.data_ptr()), rows.shape[0], ctypes.c_void_p(units.data_ptr()),
+                       units.numel(), ctypes.c_void_p(recs.data_ptr()), recs.numel()), name)
         return (row_off, rows[: int(row_off[n])], text_off, units[: int(text_off[n])], word_off,
                 recs[: int(word_off[n])])
 
@@ -938,6 +956,48 @@ class MergeTreeBatch:
         out = np.zeros(2, dtype=np.float32)
         self._check(self.lib.mt_last_walk_ms(self.h, _native.ptr(out)), "mt_last_walk_ms")
         return float(out[0]), float(out[1])
+
+    def last_walk_view(self):
+        """(queries, of them answered on the host, remote queries that started by a page skip,
+        count ms, gather ms) of the last walk_segments / walk_segments_device call."""
+        out = np.zeros(3, dtype=np.int64)
+        ms = np.zeros(2, dtype=np.float32)
+        self._check(self.lib.mt_last_walk_view(self.h, _native.ptr(out), _native.ptr(ms)), "mt_last_walk_view")
+        return int(out[0]), int(out[1]), int(out[2]), float(ms[0]), float(ms[1])
+
+    def get_texts_view(self, docs, start, end, ref_seq, client, placeholder=""):
+        """MergeTreeTextHelper.getText(refSeq, clientId, placeholder, start, end) for each query,
+        built on the host from one walk_segments call in the view, as gatherText clips
+        (MT/textSegment.ts:241-263): a visited text row gives its whole text when start <= 0 and
+        end >= its length, else substring(max(start, 0)) when end >= its length, else
+        substring(start, end) with JavaScript's swap of the two when end < start; a marker gives
+        the placeholder once per unit of its length ("" gives nothing; "*" is not offered)."""
+        if placeholder == "*":
+            raise ValueError('get_texts_view: the "*" placeholder is not offered')
+        row_off, rows, text_off, units, _, _ = self.walk_segments(docs, start, end, props=False, ref_seq=ref_seq,
+                                                                  client=client)
+        raw = units.tobytes()
+        out = []
+        for q in range(len(row_off) - 1):
+            t0, parts = int(text_off[q]), []
+            for r in rows[int(row_off[q]):int(row_off[q + 1])]:
+                ln, s, e = int(r["length"]), int(r["start"]), int(r["end"])
+                if r["marker_ref_type"] >= 0:
+                    parts.append(placeholder * ln)
+                    continue
+                lo = t0 + int(r["text"])
+                text = raw[2 * lo: 2 * (lo + ln)].decode("utf-16-le", errors="surrogatepass")
+                if s <= 0 and e >= ln:
+                    parts.append(text)
+                    continue
+                s = max(s, 0)
+                if e >= ln:
+                    parts.append(text[s:])
+                else:   # String.prototype.substring: both clamped into [0, length], swapped when start > end
+                    a, b = min(max(s, 0), ln), min(max(e, 0), ln)
+                    parts.append(text[min(a, b):max(a, b)])
+            out.append("".join(parts))
+        return out
 
     def get_prop_runs(self, doc):
         nr, nw = ctypes.c_uint32(), ctypes.c_uint32()

@@ -57,6 +57,7 @@ WALK_ROW_DTYPE = np.dtype([("row", "<i4"), ("uid", "<u4"), ("position", "<i4"), 
                            ("client", "<i4"), ("marker_ref_type", "<i4"), ("text", "<u4"), ("props", "<u4"),
                            ("start", "<i4"), ("end", "<i4"), ("flags", "<u4")])
 MT_WALK_TEXT, MT_WALK_PROPS = 1, 2
+MT_WALK_HOST = 1   # mt_walk_row.flags: answered on the host (mt_walk_segments_view)
 
 # mt_delta_range (include/mt_replay.h): one delta segment of mt_get_delta_logs' rows
 DELTA_RANGE_DTYPE = np.dtype([("query", "<i4"), ("record", "<i4"), ("seq", "<i4"), ("kind", "<i4"),
@@ -182,6 +183,9 @@ SIGNATURES = [
     ("mt_walk_segments", _I, [_P, _U32, _P, _P, _P, _U32, _P, _P, _P, _P, _U64, _P, _U64, _P, _U64]),
     ("mt_walk_segments_device", _I, [_P, _U32, _P, _P, _P, _U32, _P, _P, _P, _P, _U64, _P, _U64, _P, _U64]),
     ("mt_last_walk_ms", _I, [_P, _P]),
+    ("mt_walk_segments_view", _I, [_P, _U32, _P, _P, _P, _P, _P, _U32, _P, _P, _P, _P, _U64, _P, _U64, _P, _U64]),
+    ("mt_walk_segments_view_device", _I, [_P, _U32, _P, _P, _P, _P, _P, _U32, _P, _P, _P, _P, _U64, _P, _U64, _P, _U64]),
+    ("mt_last_walk_view", _I, [_P, _P, _P]),
 ]
 
 _lib = None

@@ -865,17 +865,43 @@ __device__ __forceinline__ void walk_seek(const SegRanges &R, int s, int skip, i
 }
 struct WalkLane {
     bool vis;        // the lane's row is visited
-    int p0;          // its observer position
+    int p0;          // its position in the view (the observer position in the replica's own)
     int units;       // text units it contributes (its whole text; 0: a marker, or text not asked for)
     int wc;          // words of its property record (0: none, or not asked for)
     v4i a;
     v4u b;
 };
+// The (refSeq, client) view of a query (k_walk_count<true> / k_walk_gather<true>, DESIGN section
+// 26): a row's length is vl = (ins & !gone) ? len : 0 with ins / gone as loc_chunk has them, its
+// partial term pl = len * (ins - gone); N = sum pl, L = sum vl.  N == L: every interior length is
+// the non-negative sum of its leaves' vl and nodeMap's test on the shifted start / end is the
+// flat one on the vl prefix; else the query is marked for the host (host_map).  local: the
+// replica's own view (client 0), which walks as k_walk_count<false> does.
+#define MT_WALKQ_HOST 1      // mark: a view with N != L, answered on the host
+#define MT_WALKQ_INVALID 2   // mark: a remote refSeq outside [minSeq, currentSeq]
+#define MT_WALKQ_SKIP 4      // mark: a remote walk that starts at the page the table-based seek found
+struct WalkView {          // wave-uniform
+    bool local;
+    int r, c, cs;          // refSeq, short client, the client's overlap slot (0: none)
+    const uint16_t *ovf;   // the document's overflow sets (paged documents)
+    int OA;
+};
+template <bool kView> struct WalkViewArgs {};
+template <> struct WalkViewArgs<true> {
+    const int32_t *ref_seq, *client;   // [nq]
+    int32_t *mark;                     // [nq]: written by the count pass, read by the gather
+    int32_t *seek;                     // [nq][3]: a page-skip start {range, position, rows} (mark MT_WALKQ_SKIP)
+    int lds_pages;                     // page ids the count pass's dynamic LDS array holds
+};
+__device__ static bool loc_ovf_member(const uint16_t *ovf, int OA, u64 o, int c);
 // lane's row i of a range of n rows; pos is the chunk's first position, advanced past it.  A row
 // past the count is loaded from index 0 and masked; the record's count word is loaded
-// unconditionally (record 0 for a handle outside the arena) and masked.
-__device__ __forceinline__ WalkLane walk_chunk(const v4i *A, const v4u *Bv, int i, int n, const WalkQuery &Q,
-                                               uint32_t what, const uint32_t *pr, uint32_t P, int &pos) {
+// unconditionally (record 0 for a handle outside the arena) and masked, and
+// so is, in a view, the row's overlap mask.  nacc: (per lane) its rows' terms of N.
+template <bool kView>
+__device__ __forceinline__ WalkLane walk_chunk(const v4i *A, const u64 *O, const v4u *Bv, int i, int n,
+                                               const WalkQuery &Q, const WalkView &V, uint32_t what,
+                                               const uint32_t *pr, uint32_t P, int &pos, int &nacc) {
     WalkLane L;
     const bool v = i < n;
     const int ic = v ? i : 0;
@@ -885,7 +911,18 @@ __device__ __forceinline__ WalkLane walk_chunk(const v4i *A, const v4u *Bv, int 
         L.a = v4i{0, 0, MT_RSEQ_NONE, 0};
         L.b = v4u{0u, 0u, 0u, 0u};
     }
-    const int ol = obs_len(L.a);
+    int ol = obs_len(L.a);
+    if constexpr (kView) {
+        u64 o = O[ic];
+        if (!v) o = 0ull;
+        bool ovl = ovl_has(o, V.cs);
+        if (o & MT_OVF_BIT) ovl = loc_ovf_member(V.ovf, V.OA, o, V.c);
+        const bool ins = (seg_cli(L.a) == V.c) | ((L.a.y != -1) & (L.a.y <= V.r));
+        const bool gone = (L.a.z != MT_RSEQ_NONE) & ((seg_rcli(L.a) == V.c) | ovl | ((L.a.z != -1) & (L.a.z <= V.r)));
+        const int vl = (ins & !gone) ? L.a.x : 0, pl = L.a.x * ((int)ins - (int)gone);
+        nacc += V.local ? ol : pl;
+        ol = V.local ? ol : vl;   // (from here on: the row's length in the view)
+    }
     const int incl = wave_scan_incl(ol);
     L.p0 = pos + incl - ol;
     pos += bcast(incl, 63);
@@ -898,28 +935,139 @@ __device__ __forceinline__ WalkLane walk_chunk(const v4i *A, const v4u *Bv, int 
     L.wc = (L.vis & ok & ((what & MT_WALK_PROPS) != 0u)) ? 1 + 2 * (int)c : 0;
     return L;
 }
+// query q's view: false with the mark when its refSeq lies outside the document's collab window
+template <bool kView>
+__device__ __forceinline__ bool walk_view(const DevState &st, int q, int doc, const WalkViewArgs<kView> &va, WalkView &V) {
+    V.local = true;
+    V.r = V.c = V.cs = V.OA = 0;
+    V.ovf = nullptr;
+    if constexpr (kView) {
+        V.c = va.client[q];
+        V.r = va.ref_seq[q];
+        V.local = V.c == 0;
+        if (V.local) return true;
+        const DocHdr h = st.hdr[doc];
+        if (V.r < h.min_seq || V.r > h.cur_seq) return false;
+        const u64 sm = ballot(st.oslot[((size_t)doc * MT_OSLOTS + lane()) * 2] == V.c);
+        V.cs = sm ? first_lane(sm) + 1 : 0;
+        if (h.pad[HDR_PAGED]) {
+            const PagedBase pb = doc_paged(st, doc);
+            V.ovf = pb.ovf;
+            V.OA = pb.OA;
+        }
+    }
+    return true;
+}
+// A paged document's remote view from its unsettled-segment table (pg_store leaves it in HBM on
+// every paged tier, HDR_UTN entries {page id, row stamps, overlap mask}; the growth step copies
+// it): a row whose view length differs from its observer length is unsettled -- seq or
+// removedSeq above minSeq -- so it has an entry, and an entry of a row that has settled since
+// contributes 0 in every legal view (refSeq >= minSeq).  One pass, 64 entries at a time, gives
+// the anomalous length sum len * (gone & !ins) (non-zero: N != L, the host answers) and adds
+// each entry's vl - obs_len to diff[page id] (LDS).  Entries past the count read entry 0 and are
+// masked; a page id outside the array is dropped (never seen: pg_load
+// refuses such a document).
+__device__ __forceinline__ int walk_table(const PagedBase &pb, int utn, const WalkView &V, int *diff) {
+    for (int i = lane(); i < pb.PP; i += MT_WAVE) diff[i] = 0;
+    __syncthreads();
+    int anom = 0;
+    for (int base = 0; base < utn; base += MT_WAVE) {
+        const int e = base + lane();
+        const bool v = e < utn;
+        const int ec = v ? e : 0;
+        const int pg = pb.upage[ec];
+        v4i a = pb.uA[ec];
+        u64 o = pb.uO[ec];
+        if (!v) {
+            a = v4i{0, 0, MT_RSEQ_NONE, 0};
+            o = 0ull;
+        }
+        bool ovl = ovl_has(o, V.cs);
+        if (o & MT_OVF_BIT) ovl = loc_ovf_member(V.ovf, V.OA, o, V.c);
+        const bool ins = (seg_cli(a) == V.c) | ((a.y != -1) & (a.y <= V.r));
+        const bool gone = (a.z != MT_RSEQ_NONE) & ((seg_rcli(a) == V.c) | ovl | ((a.z != -1) & (a.z <= V.r)));
+        const int d = ((ins & !gone) ? a.x : 0) - obs_len(a);
+        anom += (gone & !ins) ? a.x : 0;
+        if (v && d != 0 && (uint32_t)pg < (uint32_t)pb.PP) atomicAdd(&diff[pg], d);
+    }
+    __syncthreads();
+    return wave_sum(anom);
+}
+// walk_seek on the view's page lengths PageMeta.obs + diff[page id]
+__device__ __forceinline__ void walk_seek_view(const SegRanges &R, const int *diff, int PP, int s, int &r0, int &pos,
+                                               int &rows) {
+    r0 = pos = rows = 0;
+    bool at = false;
+    for (int base = 0; !at && base < R.nr; base += MT_WAVE) {
+        const int j = base + lane();
+        const bool v = j < R.nr;
+        const int pg = R.dir[v ? j : 0];
+        const PageMeta pm = R.meta[pg];
+        const int ob = v ? pm.obs + diff[(uint32_t)pg < (uint32_t)PP ? pg : 0] * ((uint32_t)pg < (uint32_t)PP) : 0, ns = v ? (int)pm.nseg : 0;
+        const int oin = wave_scan_incl(ob), nin = wave_scan_incl(ns);
+        const u64 m = ballot(v & (pos + oin > s));
+        if (m) {
+            const int l = first_lane(m);
+            r0 = base + l;
+            pos += bcast(oin - ob, l);
+            rows += bcast(nin - ns, l);
+            at = true;
+        } else {
+            pos += bcast(oin, 63);
+            rows += bcast(nin, 63);
+        }
+    }
+    if (!at) r0 = R.nr;
+}
+// A remote view of a flat document, of a paged one whose page capacity does not fit the LDS
+// array, or under MT_LOCATE_ROW_WALK=1 walks every row from row 0 in the count pass (N and L
+// are sums over the rows) and starts its gather at row 0.  A remote view of any other paged
+// document decides N != L from the table, seeks its first page on the view's page lengths and
+// stops at the end; the gather starts where the count pass did (va.seek).  The replica's own
+// view walks as k_walk_count<false> does.
+template <bool kView>
 __global__ void __launch_bounds__(MT_WAVE) k_walk_count(DevState st, int nq, const uint32_t *docs, const int32_t *start,
                                                         const int32_t *end, uint32_t what, int skip, int64_t *n_rows,
-                                                        int64_t *n_units, int64_t *n_words, int32_t *end_seen) {
+                                                        int64_t *n_units, int64_t *n_words, int32_t *end_seen,
+                                                        WalkViewArgs<kView> va) {
+    extern __shared__ int s_diff[];
     const int q = blockIdx.x;
     if (q >= nq) return;
     const WalkQuery Q = walk_query(st, q, docs, start, end);
-    int rows_n = 0, units = 0, words = 0, pos = 0;
-    if (Q.e > 0) {
+    WalkView V;
+    const bool legal = walk_view<kView>(st, q, Q.doc, va, V);
+    bool full = kView && !V.local;   // every row is read: N and L
+    int rows_n = 0, units = 0, words = 0, pos = 0, nacc = 0, mark = legal ? 0 : MT_WALKQ_INVALID;
+    if (legal && (Q.e > 0 || full)) {
         const DocHdr h = st.hdr[Q.doc];
         const SegRanges R = seg_ranges(st, Q.doc, h);
         const PagedBase ar = doc_paged(st, Q.doc);   // (the arenas of the document's region)
         const uint32_t P = (uint32_t)ar.P;
         const uint32_t *pr = ar.props + (size_t)h.props_half * P * MT_PREC;
-        int r0, rows;
-        walk_seek(R, Q.s, skip, r0, pos, rows);
-        for (int r = r0; r < R.count() && pos < Q.e; r++) {
+        int r0 = 0, rows = 0;
+        bool host = false;
+        if constexpr (kView) {
+            if (full && skip && R.paged && ar.PP <= va.lds_pages) {
+                host = walk_table(ar, min(max(h.pad[HDR_UTN], 0), ar.UT), V, s_diff) != 0;
+                full = false;
+                mark = MT_WALKQ_SKIP;
+                if (!host) walk_seek_view(R, s_diff, ar.PP, Q.s, r0, pos, rows);
+                if (lane() == 0) {
+                    va.seek[3 * q] = r0;
+                    va.seek[3 * q + 1] = pos;
+                    va.seek[3 * q + 2] = rows;
+                }
+            }
+        }
+        if (mark != MT_WALKQ_SKIP) walk_seek(R, Q.s, full ? 0 : skip, r0, pos, rows);
+        for (int r = r0; !host && r < R.count() && (full || pos < Q.e); r++) {
             const v4i *A;
             const v4u *Bv;
             int n;
             R.get(r, A, Bv, n);
-            for (int base = 0; base < n && pos < Q.e; base += MT_WAVE) {
-                const WalkLane L = walk_chunk(A, Bv, base + lane(), n, Q, what, pr, P, pos);
+            const u64 *O = R.O + (A - R.A);
+            for (int base = 0; base < n && (full || pos < Q.e); base += MT_WAVE) {
+                const WalkLane L = walk_chunk<kView>(A, O, Bv, base + lane(), n, Q, V, what, pr, P, pos, nacc);
                 rows_n += __popcll(ballot(L.vis));
                 units += L.units;
                 words += L.wc;
@@ -927,12 +1075,17 @@ __global__ void __launch_bounds__(MT_WAVE) k_walk_count(DevState st, int nq, con
         }
         units = wave_sum(units);
         words = wave_sum(words);
+        if (host || (full && wave_sum(nacc) != pos)) {   // N != L: the host answers, counts included
+            mark = MT_WALKQ_HOST;
+            rows_n = units = words = 0;
+        }
     }
     if (lane() == 0) {
         n_rows[q] = rows_n;
         n_units[q] = units;
         n_words[q] = words;
         end_seen[q] = Q.open ? pos : Q.e;   // (an open walk ran to the document's end: pos is its length)
+        if constexpr (kView) va.mark[q] = mark;
     }
 }
 // Writes query q's records at rows[row_off[q] ..), its texts at text[text_off[q] ..) and its
@@ -947,16 +1100,26 @@ __global__ void __launch_bounds__(MT_WAVE) k_walk_count(DevState st, int nq, con
 // helper would recompile a kernel whose timing is recorded.)  Rows, units and words are checked
 // against the query's three slots: the state cannot change between the passes, but a wrong count
 // must not become a store outside the result.
+template <bool kView>
 __global__ void __launch_bounds__(MT_WAVE) k_walk_gather(DevState st, int nq, const uint32_t *docs,
                                                          const int32_t *start, const int32_t *end, uint32_t what,
                                                          int skip, const int32_t *end_seen, const int64_t *row_off,
                                                          const int64_t *text_off, const int64_t *word_off,
                                                          mt_walk_row *rows_out, uint16_t *text_out,
-                                                         uint32_t *records) {
+                                                         uint32_t *records, WalkViewArgs<kView> va) {
     __shared__ int s_dst[MT_WAVE], s_src[MT_WAVE];
     const int q = blockIdx.x;
     if (q >= nq) return;
     WalkQuery Q = walk_query(st, q, docs, start, end);
+    WalkView V;
+    bool took = false;   // the count pass started at a page the table-based seek found
+    if constexpr (kView) {
+        const int mk = va.mark[q];
+        if (mk & (MT_WALKQ_HOST | MT_WALKQ_INVALID)) return;   // (the host writes a marked query's slots)
+        took = mk == MT_WALKQ_SKIP;
+    }
+    walk_view<kView>(st, q, Q.doc, va, V);
+    int nacc = 0;
     const int64_t room_r = row_off[q + 1] - row_off[q], room_t = text_off[q + 1] - text_off[q],
                   room_w = word_off[q + 1] - word_off[q];
     if (Q.e <= 0 || room_r <= 0) return;
@@ -981,7 +1144,14 @@ __global__ void __launch_bounds__(MT_WAVE) k_walk_gather(DevState st, int nq, co
         return ix < T ? tb[ix] : 0u;
     };
     int r0, pos, rows;
-    walk_seek(R, Q.s, skip, r0, pos, rows);
+    walk_seek(R, Q.s, kView && !V.local ? 0 : skip, r0, pos, rows);
+    if constexpr (kView) {
+        if (took) {
+            r0 = min(max(va.seek[3 * q], 0), R.count());
+            pos = va.seek[3 * q + 1];
+            rows = va.seek[3 * q + 2];
+        }
+    }
     int64_t rows_done = 0, words_done = 0;
     int64_t done = 0;        // units of the query produced so far (the carried one included)
     bool carry = false;      // unit done - 1 is the first half of a word not yet stored
@@ -991,8 +1161,9 @@ __global__ void __launch_bounds__(MT_WAVE) k_walk_gather(DevState st, int nq, co
         const v4u *Bv;
         int n;
         R.get(r, A, Bv, n);
+        const u64 *O = R.O + (A - R.A);
         for (int base = 0; base < n && pos < Q.e; base += MT_WAVE) {
-            const WalkLane L = walk_chunk(A, Bv, base + lane(), n, Q, what, pr, P, pos);
+            const WalkLane L = walk_chunk<kView>(A, O, Bv, base + lane(), n, Q, V, what, pr, P, pos, nacc);
             const u64 vm = ballot(L.vis);
             if (!vm) continue;
             const int incl = wave_scan_incl(L.units), winc = wave_scan_incl(L.wc);
@@ -1789,6 +1960,8 @@ struct mt_handle {
     uint32_t *d_rst = nullptr;   // mt_delta_log_reset_docs: the listed documents (rst_cap of them)
     uint32_t rst_cap = 0;
     int64_t loc_n = 0, loc_host = 0;   // queries of the last segment read-out, of them answered by the host path
+    int64_t wv_n = 0, wv_host = 0, wv_skip = 0;   // queries of the last walk in a view, of them answered by the
+                                                  // host path / started by the table-based page seek
     int64_t tile_n = 0, tile_rows = 0;   // queries of the last marker query, rows its kernel examined
     // documents per workgroup of the LDS-tier replay (env MT_WPG=2 for two): measured on C2
     // the CU saturates at 16 resident documents (16 -> 18 per CU: 61.8 -> 64.6 ms)
@@ -4047,31 +4220,59 @@ int mt_last_props_ms(mt_handle *h, float *out) {
 // mt_walk_segments / mt_walk_segments_device: get_prop_runs_bulk's shape with three counts per
 // query (rows, text units, record words), so three prefix sums and three outputs; the count
 // pass also leaves every query's end as the leaf action sees it for the gather.
-static int walk_segments(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
-                         uint32_t what, int64_t *row_off, int64_t *text_off, int64_t *word_off, void *rows,
-                         uint64_t cap_rows, void *text, uint64_t cap_text, void *records, uint64_t cap_words,
-                         bool device) {
+// mt_walk_segments_view*: the same in a (refSeq, client) view per query.  The count pass marks the
+// queries of views with N != L; their visit lists and counts are computed here (walk_on_host,
+// below host_search) and patched into the counts before the prefix sums, the gather skips them
+// and their rows, texts and records are written into their slots after it.
+struct HostWalk {   // a query answered on the host
+    uint32_t q;
+    std::vector<mt_walk_row> rows;
+    std::vector<uint16_t> text;
+    std::vector<uint32_t> recs;
+};
+static int walk_on_host(mt_handle *h, std::vector<uint32_t> todo, const uint32_t *docs, const int32_t *start,
+                        const int32_t *end, const int32_t *ref_seq, const int32_t *client, uint32_t what,
+                        std::vector<HostWalk> &out);
+static int walk_segments(mt_handle *h, const char *name, uint32_t n, const uint32_t *docs, const int32_t *start,
+                         const int32_t *end, const int32_t *ref_seq, const int32_t *client, uint32_t what,
+                         int64_t *row_off, int64_t *text_off, int64_t *word_off, void *rows, uint64_t cap_rows,
+                         void *text, uint64_t cap_text, void *records, uint64_t cap_words, bool device) {
     if (!h || !row_off || !text_off || !word_off) return MT_E_INVALID;
-    if (what & ~(MT_WALK_TEXT | MT_WALK_PROPS)) {
-        h->err = "mt_walk_segments: undefined bits in what (" + std::to_string(what) + ")";
+    if ((ref_seq == nullptr) != (client == nullptr)) {
+        h->err = std::string(name) + ": ref_seq and client are both NULL or both given";
         return MT_E_INVALID;
     }
-    int rc = check_queries(h, "mt_walk_segments", n, docs);
+    if (what & ~(MT_WALK_TEXT | MT_WALK_PROPS)) {
+        h->err = std::string(name) + ": undefined bits in what (" + std::to_string(what) + ")";
+        return MT_E_INVALID;
+    }
+    int rc = check_queries(h, name, n, docs);
     if (rc) return rc;
     for (uint32_t q = 0; start && q < n; q++)
         if (start[q] < 0) {
-            h->err = "mt_walk_segments: query " + std::to_string(q) + ": start below 0";
+            h->err = std::string(name) + ": query " + std::to_string(q) + ": start below 0";
             return MT_E_INVALID;
         }
+    bool view = false;   // some query asks for a view other than the replica's own
+    for (uint32_t q = 0; client && q < n; q++) {
+        if (client[q] < 0) {
+            h->err = std::string(name) + ": query " + std::to_string(q) + ": negative client";
+            return MT_E_INVALID;
+        }
+        view = view || client[q] != 0;
+    }
     HIPCHK(h, hipSetDevice(h->device));
     SETTLE(h);
     ReadTimer &tm = h->tm_walk;
     tm.timed = 0;
+    h->wv_n = n;
+    h->wv_host = h->wv_skip = 0;
     if (n == 0) return empty_offsets(h, {row_off, text_off, word_off}, device);
-    // extra: the three counts [n] each, the three offset arrays [n + 1] each, the ends [n]
+    // extra: the three counts [n] each, the three offset arrays [n + 1] each, the ends [n]; in a
+    // view the refSeqs, the clients and the marks [n] each
     const size_t cnt_w = (size_t)n * 3, off_w = ((size_t)n + 1) * 3, end_b = ((size_t)n * 4 + 7) & ~(size_t)7;
     QueryCols qc;
-    HIPCHK(h, qc.upload(n, {docs, start, end}, (cnt_w + off_w) * 8 + end_b));
+    HIPCHK(h, qc.upload(n, {docs, start, end}, (cnt_w + off_w) * 8 + end_b * (view ? 7 : 1)));
     const uint32_t *d_docs = (const uint32_t *)qc.col[0];
     const int32_t *d_start = (const int32_t *)qc.col[1], *d_end = (const int32_t *)qc.col[2];
     int64_t *base = (int64_t *)qc.extra;
@@ -4080,14 +4281,58 @@ static int walk_segments(mt_handle *h, uint32_t n, const uint32_t *docs, const i
     int64_t *d_off[3];
     for (int i = 0; i < 3; i++) d_off[i] = device ? off[i] : base + cnt_w + (size_t)i * (n + 1);
     int32_t *d_ends = (int32_t *)(base + cnt_w + off_w);
+    WalkViewArgs<false> no_view;
+    WalkViewArgs<true> va{nullptr, nullptr, nullptr, nullptr, 0};
+    // the page ids the count pass's LDS array holds: the handle's page capacities, 32 KB at the most
+    const int lds_pages = view ? std::min(std::max({(int)h->st.PP, (int)h->st.big.PP, 1}), 8192) : 0;
+    if (view) {
+        uint8_t *vb = (uint8_t *)d_ends + end_b;
+        HIPCHK(h, hipMemcpy(vb, ref_seq, (size_t)n * 4, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(vb + end_b, client, (size_t)n * 4, hipMemcpyHostToDevice));
+        va = WalkViewArgs<true>{(const int32_t *)vb, (const int32_t *)(vb + end_b), (int32_t *)(vb + 2 * end_b),
+                                (int32_t *)(vb + 3 * end_b), lds_pages};
+    }
     // MT_LOCATE_ROW_WALK=1: walk from row 0 (the A/B of tools/walk_probe.py)
     const char *rw = getenv("MT_LOCATE_ROW_WALK");
     const int skip = !(rw && rw[0] == '1');
     HIPCHK(h, tm.begin(0, h->stream));
-    hipLaunchKernelGGL(k_walk_count, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start, d_end, what,
-                       skip, d_cnt[0], d_cnt[1], d_cnt[2], d_ends);
+    if (view)
+        hipLaunchKernelGGL(k_walk_count<true>, dim3(n), dim3(MT_WAVE), (size_t)lds_pages * 4, h->stream, h->st, (int)n, d_docs, d_start,
+                           d_end, what, skip, d_cnt[0], d_cnt[1], d_cnt[2], d_ends, va);
+    else
+        hipLaunchKernelGGL(k_walk_count<false>, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start,
+                           d_end, what, skip, d_cnt[0], d_cnt[1], d_cnt[2], d_ends, no_view);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, tm.end(0, h->stream));
+    std::vector<HostWalk> hw;
+    if (view) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        std::vector<int32_t> mark(n);
+        HIPCHK(h, hipMemcpy(mark.data(), va.mark, (size_t)n * 4, hipMemcpyDeviceToHost));
+        std::vector<uint32_t> todo;
+        for (uint32_t q = 0; q < n; q++) {
+            if (mark[q] == MT_WALKQ_INVALID) {
+                h->err = std::string(name) + ": query " + std::to_string(q) + ": remote view of document " +
+                         std::to_string(docs ? docs[q] : q) + " with refSeq " + std::to_string(ref_seq[q]) +
+                         " outside the collab window [minSeq, currentSeq]";
+                return MT_E_INVALID;
+            }
+            if (mark[q] == MT_WALKQ_HOST) todo.push_back(q);
+            h->wv_skip += mark[q] == MT_WALKQ_SKIP;
+        }
+        if ((rc = walk_on_host(h, todo, docs, start, end, ref_seq, client, what, hw))) return rc;
+        if (!hw.empty()) {   // the three count arrays are adjacent: one copy each way
+            std::vector<int64_t> cnt(cnt_w);
+            HIPCHK(h, hipMemcpy(cnt.data(), base, cnt_w * 8, hipMemcpyDeviceToHost));
+            for (const HostWalk &w : hw) {
+                cnt[w.q] = (int64_t)w.rows.size();
+                cnt[(size_t)n + w.q] = (int64_t)w.text.size();
+                cnt[2 * (size_t)n + w.q] = (int64_t)w.recs.size();
+            }
+            HIPCHK(h, hipMemcpy(base, cnt.data(), cnt_w * 8, hipMemcpyHostToDevice));
+        }
+        h->wv_host = (int64_t)hw.size();
+    }
     int64_t total[3] = {0, 0, 0};
     if ((rc = scan_counts(h, n, 3, d_cnt, off, device, total))) return rc;
     tm.timed = 1;
@@ -4095,9 +4340,10 @@ static int walk_segments(mt_handle *h, uint32_t n, const uint32_t *docs, const i
     if (!records) cap_words = 0;
     const bool fits = cap_rows >= (uint64_t)total[0] && cap_text >= (uint64_t)total[1] && cap_words >= (uint64_t)total[2];
     rc = after_counts(h, !rows, fits, total[0] == 0, [&] {
-        return "mt_walk_segments: the outputs hold " + std::to_string(cap_rows) + " rows, " + std::to_string(cap_text) +
-               " text units and " + std::to_string(cap_words) + " words, the results need " + std::to_string(total[0]) +
-               " rows, " + std::to_string(total[1]) + " text units and " + std::to_string(total[2]) + " words";
+        return std::string(name) + ": the outputs hold " + std::to_string(cap_rows) + " rows, " +
+               std::to_string(cap_text) + " text units and " + std::to_string(cap_words) + " words, the results need " +
+               std::to_string(total[0]) + " rows, " + std::to_string(total[1]) + " text units and " +
+               std::to_string(total[2]) + " words";
     });
     if (rc != RO_GATHER) return rc;
     if (!device)
@@ -4110,13 +4356,34 @@ static int walk_segments(mt_handle *h, uint32_t n, const uint32_t *docs, const i
     HIPCHK(h, g_text.open(text, device, (size_t)total[1]));
     HIPCHK(h, g_recs.open(records, device, (size_t)total[2]));
     HIPCHK(h, tm.begin(1, h->stream));
-    hipLaunchKernelGGL(k_walk_gather, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start, d_end, what,
-                       skip, (const int32_t *)d_ends, (const int64_t *)d_off[0], (const int64_t *)d_off[1],
-                       (const int64_t *)d_off[2], g_rows.p, g_text.p, g_recs.p);
+    if (view)
+        hipLaunchKernelGGL(k_walk_gather<true>, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start,
+                           d_end, what, skip, (const int32_t *)d_ends, (const int64_t *)d_off[0],
+                           (const int64_t *)d_off[1], (const int64_t *)d_off[2], g_rows.p, g_text.p, g_recs.p, va);
+    else
+        hipLaunchKernelGGL(k_walk_gather<false>, dim3(n), dim3(MT_WAVE), 0, h->stream, h->st, (int)n, d_docs, d_start,
+                           d_end, what, skip, (const int32_t *)d_ends, (const int64_t *)d_off[0],
+                           (const int64_t *)d_off[1], (const int64_t *)d_off[2], g_rows.p, g_text.p, g_recs.p, no_view);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, tm.end(1, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     tm.timed = 2;
+    // the host-answered queries' slots (the offsets' totals hold their counts, so the capacities
+    // were checked with them): into the staged outputs, which copy_out then hands over
+    std::vector<int64_t> offs_dev;   // (the _device form: the offsets are in device memory)
+    if (device && !hw.empty()) {
+        offs_dev.resize(3 * ((size_t)n + 1));
+        for (int i = 0; i < 3; i++)
+            HIPCHK(h, hipMemcpy(offs_dev.data() + (size_t)i * (n + 1), off[i], ((size_t)n + 1) * 8, hipMemcpyDeviceToHost));
+    }
+    for (const HostWalk &w : hw) {
+        int64_t o3[3];
+        for (int i = 0; i < 3; i++) o3[i] = device ? offs_dev[(size_t)i * (n + 1) + w.q] : off[i][w.q];
+        if (!w.rows.empty())
+            HIPCHK(h, hipMemcpy(g_rows.p + o3[0], w.rows.data(), w.rows.size() * sizeof(mt_walk_row), hipMemcpyHostToDevice));
+        if (!w.text.empty()) HIPCHK(h, hipMemcpy(g_text.p + o3[1], w.text.data(), w.text.size() * 2, hipMemcpyHostToDevice));
+        if (!w.recs.empty()) HIPCHK(h, hipMemcpy(g_recs.p + o3[2], w.recs.data(), w.recs.size() * 4, hipMemcpyHostToDevice));
+    }
     HIPCHK(h, g_rows.copy_out(rows, (size_t)total[0]));
     HIPCHK(h, g_text.copy_out(text, (size_t)total[1]));
     HIPCHK(h, g_recs.copy_out(records, (size_t)total[2]));
@@ -4126,16 +4393,44 @@ static int walk_segments(mt_handle *h, uint32_t n, const uint32_t *docs, const i
 int mt_walk_segments(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
                      uint32_t what, int64_t *row_off, int64_t *text_off, int64_t *word_off, mt_walk_row *rows,
                      uint64_t cap_rows, uint16_t *text, uint64_t cap_text, uint32_t *records, uint64_t cap_words) {
-    return walk_segments(h, n, docs, start, end, what, row_off, text_off, word_off, rows, cap_rows, text, cap_text,
-                         records, cap_words, false);
+    return walk_segments(h, "mt_walk_segments", n, docs, start, end, nullptr, nullptr, what, row_off, text_off, word_off,
+                         rows, cap_rows, text, cap_text, records, cap_words, false);
 }
 
 int mt_walk_segments_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
                             uint32_t what, void *row_off_dev, void *text_off_dev, void *word_off_dev, void *rows_dev,
                             uint64_t cap_rows, void *text_dev, uint64_t cap_text, void *records_dev,
                             uint64_t cap_words) {
-    return walk_segments(h, n, docs, start, end, what, (int64_t *)row_off_dev, (int64_t *)text_off_dev,
-                         (int64_t *)word_off_dev, rows_dev, cap_rows, text_dev, cap_text, records_dev, cap_words, true);
+    return walk_segments(h, "mt_walk_segments", n, docs, start, end, nullptr, nullptr, what, (int64_t *)row_off_dev,
+                         (int64_t *)text_off_dev, (int64_t *)word_off_dev, rows_dev, cap_rows, text_dev, cap_text,
+                         records_dev, cap_words, true);
+}
+
+int mt_walk_segments_view(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
+                          const int32_t *ref_seq, const int32_t *client, uint32_t what, int64_t *row_off,
+                          int64_t *text_off, int64_t *word_off, mt_walk_row *rows, uint64_t cap_rows, uint16_t *text,
+                          uint64_t cap_text, uint32_t *records, uint64_t cap_words) {
+    return walk_segments(h, "mt_walk_segments_view", n, docs, start, end, ref_seq, client, what, row_off, text_off,
+                         word_off, rows, cap_rows, text, cap_text, records, cap_words, false);
+}
+
+int mt_walk_segments_view_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start,
+                                 const int32_t *end, const int32_t *ref_seq, const int32_t *client, uint32_t what,
+                                 void *row_off_dev, void *text_off_dev, void *word_off_dev, void *rows_dev,
+                                 uint64_t cap_rows, void *text_dev, uint64_t cap_text, void *records_dev,
+                                 uint64_t cap_words) {
+    return walk_segments(h, "mt_walk_segments_view", n, docs, start, end, ref_seq, client, what, (int64_t *)row_off_dev,
+                         (int64_t *)text_off_dev, (int64_t *)word_off_dev, rows_dev, cap_rows, text_dev, cap_text,
+                         records_dev, cap_words, true);
+}
+
+int mt_last_walk_view(mt_handle *h, int64_t *out, float *ms) {
+    if (!h || !out) return MT_E_INVALID;
+    out[0] = h->wv_n;
+    out[1] = h->wv_host;
+    out[2] = h->wv_skip;
+    if (ms) return read_timer(h, h->tm_walk, ms);
+    return 0;
 }
 
 int mt_last_walk_ms(mt_handle *h, float *out) {
@@ -4439,6 +4734,107 @@ static int host_search(const HostDoc &hd, const HostView &v, const HostTree &t, 
         pos -= l;
     }
     return -1;
+}
+
+// nodeMap (:2936-2998) in view v over the tree's partial lengths: a child -- interior by P, a
+// leaf by its nodeLength -- is entered when (end > 0) && (len > 0) && (start < len) holds on the
+// start and end shifted by the lengths before it, interior lengths included as they are (a block
+// holding a row that is removed but not inserted in the view is shorter than its visible leaves,
+// may be skipped outright, and shifts every later position).  The leaf action's arguments.
+struct HostVisit {
+    int row, pos, start, end;
+};
+static void host_map(const HostDoc &hd, const HostView &v, const HostTree &t, int l, int b, int &pos, int &start,
+                     int &end, std::vector<HostVisit> &out) {
+    for (int k = t.first[l][b]; k < t.first[l][b] + hd.lv[l][b]; k++) {
+        if (l == 0 ? k >= hd.hdr.n_seg : k >= (int)t.P[l - 1].size()) break;
+        const int len = l == 0 ? host_view_len(hd, v, k) : t.P[l - 1][k];
+        if (end > 0 && len > 0 && start < len) {
+            if (l == 0) {
+                out.push_back(HostVisit{k, pos, start, end});
+            } else {
+                int p = pos, s = start, e = end;
+                host_map(hd, v, t, l - 1, k, p, s, e, out);
+            }
+        }
+        pos += len;
+        start -= len;
+        end -= len;
+    }
+}
+static int walk_on_host(mt_handle *h, std::vector<uint32_t> todo, const uint32_t *docs, const int32_t *start,
+                        const int32_t *end, const int32_t *ref_seq, const int32_t *client, uint32_t what,
+                        std::vector<HostWalk> &out) {
+    auto doc_of = [&](uint32_t q) { return docs ? docs[q] : q; };
+    std::stable_sort(todo.begin(), todo.end(), [&](uint32_t a, uint32_t b) {
+        if (doc_of(a) != doc_of(b)) return doc_of(a) < doc_of(b);
+        if (client[a] != client[b]) return client[a] < client[b];
+        return ref_seq[a] < ref_seq[b];
+    });
+    HostDoc hd;
+    HostView v{0, 0, 0, false};
+    HostTree t;
+    int64_t have = -1, have_c = 0, have_r = 0;
+    std::vector<HostVisit> vis;
+    for (uint32_t q : todo) {
+        const uint32_t d = doc_of(q);
+        int rc;
+        bool fresh = false;
+        if ((int64_t)d != have) {
+            if ((rc = fetch_doc(h, d, hd, (what & MT_WALK_TEXT) != 0u, (what & MT_WALK_PROPS) != 0u))) return rc;
+            have = d;
+            fresh = true;
+        }
+        if (fresh || client[q] != have_c || ref_seq[q] != have_r) {
+            if ((rc = host_view_setup(h, d, hd, ref_seq[q], client[q], v))) return rc;
+            host_tree(hd, v, t);
+            have_c = client[q];
+            have_r = ref_seq[q];
+        }
+        out.emplace_back();
+        HostWalk &w = out.back();
+        w.q = q;
+        vis.clear();
+        if (hd.hdr.n_seg > 0 && !hd.lv.empty()) {
+            const int D = (int)hd.lv.size();
+            int pos = 0, s = start ? start[q] : 0;
+            int e = end && end[q] >= 0 ? end[q] : t.P[D - 1][0];   // an undefined end: blockLength(root)
+            host_map(hd, v, t, D - 1, 0, pos, s, e, vis);
+        }
+        const uint32_t P = (uint32_t)(hd.props.size() / MT_PREC);
+        for (const HostVisit &x : vis) {
+            const int4 a = hd.A[x.row];
+            const uint4 b = hd.B[x.row];
+            const bool marker = (b.z & MT_MARKER_BIT) != 0u;
+            mt_walk_row r;
+            r.row = x.row;
+            r.uid = b.z & ~MT_MARKER_BIT;
+            r.position = x.pos;
+            r.length = a.x;
+            r.seq = a.y >= MT_LOCAL_BASE ? -1 : a.y;
+            r.client = (int)(short)(a.w & 0xFFFF);
+            r.marker_ref_type = marker ? (int32_t)b.x : -1;
+            r.text = r.props = MT_PROPS_NONE;
+            r.start = x.start;
+            r.end = x.end;
+            r.flags = MT_WALK_HOST;
+            if ((what & MT_WALK_TEXT) && !marker && a.x > 0) {
+                r.text = (uint32_t)w.text.size();
+                for (int j = 0; j < a.x; j++) {
+                    const size_t ix = (size_t)b.x + j;
+                    w.text.push_back(ix < hd.text.size() ? hd.text[ix] : (uint16_t)0);
+                }
+            }
+            if ((what & MT_WALK_PROPS) && b.y != 0u && b.y < P && hd.props[(size_t)b.y * MT_PREC] <= (uint32_t)MT_KMAX) {
+                const uint32_t *x0 = hd.props.data() + (size_t)b.y * MT_PREC;
+                r.props = (uint32_t)w.recs.size();
+                w.recs.push_back(x0[0]);
+                for (uint32_t k = 1; k < 1 + 2 * x0[0]; k++) w.recs.push_back(x0[k]);
+            }
+            w.rows.push_back(r);
+        }
+    }
+    return 0;
 }
 
 int mt_get_containing_segment(mt_handle *h, uint32_t doc, int32_t pos, int32_t ref_seq, int32_t client,

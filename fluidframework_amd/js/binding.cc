@@ -654,15 +654,21 @@ napi_value GetPropRunsBulk(napi_env env, napi_callback_info info) {
 // end < 0 is the document's length; what: 1 text | 2 property records.  Query q's rows start at
 // rows[12 * rowOff[q]]; a row's text is text[textOff[q] + row.text ..][0 .. length), its record
 // records[wordOff[q] + row.props ..], 0xFFFFFFFF: none.)
-napi_value WalkSegments(napi_env env, napi_callback_info info) {
-    napi_value argv[5];
-    if (!get_args(env, info, 5, argv)) return nullptr;
+// walkSegmentsView(h, docs|null, start|null, end|null, refSeq|null, client|null, what): the same in
+// a (refSeq, client) view per query (mt_walk_segments_view); refSeq and client are Int32Arrays
+// with one entry per query, both null: the replica's own view.  A row's flags word (rows[12 * i +
+// 11]) is 1 when its query was answered on the host.
+static napi_value walk(napi_env env, napi_callback_info info, bool view) {
+    napi_value argv[7];
+    const int nc = view ? 5 : 3;
+    if (!get_args(env, info, nc + 2, argv)) return nullptr;
     Handle *hd = get_handle(env, argv[0]);
     if (!hd) return nullptr;
-    void *ptrs[3] = {nullptr, nullptr, nullptr};
-    size_t lens[3] = {0, 0, 0};
-    const napi_typedarray_type want[3] = {napi_uint32_array, napi_int32_array, napi_int32_array};
-    for (int i = 0; i < 3; i++) {
+    void *ptrs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t lens[5] = {0, 0, 0, 0, 0};
+    const napi_typedarray_type want[5] = {napi_uint32_array, napi_int32_array, napi_int32_array, napi_int32_array,
+                                          napi_int32_array};
+    for (int i = 0; i < nc; i++) {
         napi_valuetype vt;
         NAPI_CALL(env, napi_typeof(env, argv[1 + i], &vt));
         if (vt == napi_null || vt == napi_undefined) continue;
@@ -670,23 +676,32 @@ napi_value WalkSegments(napi_env env, napi_callback_info info) {
         napi_value ab;
         size_t off;
         if (napi_get_typedarray_info(env, argv[1 + i], &t, &lens[i], &ptrs[i], &ab, &off) != napi_ok || t != want[i]) {
-            napi_throw_type_error(env, nullptr, "walkSegments: docs is a Uint32Array, start and end are Int32Arrays (or null)");
+            napi_throw_type_error(env, nullptr, "walkSegments: docs is a Uint32Array, start, end, refSeq and client are Int32Arrays (or null)");
             return nullptr;
         }
         if (!ptrs[i]) ptrs[i] = &lens[i];   // (an empty array: any non-null pointer, never read)
     }
     uint32_t what = 0;
-    NAPI_CALL(env, napi_get_value_uint32(env, argv[4], &what));
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[nc + 1], &what));
     const size_t n = ptrs[0] ? lens[0] : mt_num_docs(hd->h);
-    if ((ptrs[1] && lens[1] != n) || (ptrs[2] && lens[2] != n)) {
-        napi_throw_range_error(env, nullptr, "walkSegments: start and end hold one entry per query");
-        return nullptr;
-    }
+    for (int i = 1; i < nc; i++)
+        if (ptrs[i] && lens[i] != n) {
+            napi_throw_range_error(env, nullptr, "walkSegments: start, end, refSeq and client hold one entry per query");
+            return nullptr;
+        }
+    const char *name = view ? "mt_walk_segments_view" : "mt_walk_segments";
+    auto call = [&](int64_t *const *off, mt_walk_row *rows, size_t nr, uint16_t *text, size_t nt, uint32_t *recs, size_t nw) {
+        if (view)
+            return mt_walk_segments_view(hd->h, (uint32_t)n, (const uint32_t *)ptrs[0], (const int32_t *)ptrs[1],
+                                         (const int32_t *)ptrs[2], (const int32_t *)ptrs[3], (const int32_t *)ptrs[4], what,
+                                         off[0], off[1], off[2], rows, nr, text, nt, recs, nw);
+        return mt_walk_segments(hd->h, (uint32_t)n, (const uint32_t *)ptrs[0], (const int32_t *)ptrs[1],
+                                (const int32_t *)ptrs[2], what, off[0], off[1], off[2], rows, nr, text, nt, recs, nw);
+    };
     std::vector<int64_t> off[3] = {std::vector<int64_t>(n + 1), std::vector<int64_t>(n + 1), std::vector<int64_t>(n + 1)};
-    int rc = mt_walk_segments(hd->h, (uint32_t)n, (const uint32_t *)ptrs[0], (const int32_t *)ptrs[1],
-                              (const int32_t *)ptrs[2], what, off[0].data(), off[1].data(), off[2].data(), nullptr, 0,
-                              nullptr, 0, nullptr, 0);
-    if (rc) return throw_rc(env, hd, rc, "mt_walk_segments");
+    int64_t *const offp[3] = {off[0].data(), off[1].data(), off[2].data()};
+    int rc = call(offp, nullptr, 0, nullptr, 0, nullptr, 0);
+    if (rc) return throw_rc(env, hd, rc, name);
     const size_t cnt[3] = {(size_t)off[0][n], (size_t)off[1][n], (size_t)off[2][n]};
     const size_t bytes[3] = {cnt[0] * sizeof(mt_walk_row), cnt[1] * 2, cnt[2] * 4};
     void *data[3], *od[3];
@@ -696,12 +711,10 @@ napi_value WalkSegments(napi_env env, napi_callback_info info) {
         NAPI_CALL(env, napi_create_arraybuffer(env, (n + 1) * 8, &od[i], &oab[i]));
     }
     uint64_t none[6] = {0, 0, 0, 0, 0, 0};   // (an empty result: any non-null pointer, never written)
-    rc = mt_walk_segments(hd->h, (uint32_t)n, (const uint32_t *)ptrs[0], (const int32_t *)ptrs[1], (const int32_t *)ptrs[2],
-                          what, off[0].data(), off[1].data(), off[2].data(),
-                          cnt[0] ? (mt_walk_row *)data[0] : (mt_walk_row *)none, cnt[0],
-                          cnt[1] ? (uint16_t *)data[1] : (uint16_t *)none, cnt[1],
-                          cnt[2] ? (uint32_t *)data[2] : (uint32_t *)none, cnt[2]);
-    if (rc) return throw_rc(env, hd, rc, "mt_walk_segments");
+    rc = call(offp, cnt[0] ? (mt_walk_row *)data[0] : (mt_walk_row *)none, cnt[0],
+              cnt[1] ? (uint16_t *)data[1] : (uint16_t *)none, cnt[1],
+              cnt[2] ? (uint32_t *)data[2] : (uint32_t *)none, cnt[2]);
+    if (rc) return throw_rc(env, hd, rc, name);
     const napi_typedarray_type types[3] = {napi_int32_array, napi_uint16_array, napi_uint32_array};
     const size_t elems[3] = {cnt[0] * (sizeof(mt_walk_row) / 4), cnt[1], cnt[2]};
     const char *names[3] = {"rows", "text", "records"}, *onames[3] = {"rowOff", "textOff", "wordOff"};
@@ -715,6 +728,8 @@ napi_value WalkSegments(napi_env env, napi_callback_info info) {
     }
     return obj;
 }
+napi_value WalkSegments(napi_env env, napi_callback_info info) { return walk(env, info, false); }
+napi_value WalkSegmentsView(napi_env env, napi_callback_info info) { return walk(env, info, true); }
 
 // locateSegments(h, docs, pos, refSeq|null, client|null) / locateUids(h, docs, uids, refSeq|null,
 // client|null) -> Int32Array, 12 words per query: the mt_seg_hit records of mt_locate_segments /
@@ -1196,7 +1211,8 @@ napi_value Init(napi_env env, napi_value exports) {
                {"extractSnapshots", ExtractSnapshots},   {"locateSegments", LocateSegments},
                {"locateUids", LocateUids},               {"resolveRemotePositions", ResolveRemotePositions},
                {"findTiles", FindTiles},                 {"findMarkersById", FindMarkersById},
-               {"walkSegments", WalkSegments}};
+               {"walkSegments", WalkSegments},
+               {"walkSegmentsView", WalkSegmentsView}};
     for (auto &f : fns) {
         napi_value v;
         NAPI_CALL(env, napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v));

@@ -479,15 +479,22 @@ class GpuMergeTreeBatch {
      * `segment` is the document's object for that segment -- cachedLength, seq, clientId, text or
      * refType, properties -- the one the delta events and getContainingSegment hand out; start
      * and end are the leaf action's arguments (the query's minus pos, not clipped to the segment).
+     * A query may name a view {refSeq, clientId} (MergeTree.mapRange's; a short client id, 0 or
+     * undefined: the replica's own): lengths, pos, start and end are then that view's
+     * (mt_walk_segments_view); refSeq must lie in the document's collab window.
      */
     walkSegments(queries) {
         this.flush();
         const nil = (v) => v === undefined || v === null;
         // (the device takes start >= 0, and an end below 0 for "the length": a start below 0
         // visits what 0 visits, an end below 1 nothing)
-        const r = native.walkSegments(this.h, Uint32Array.from(queries, (q) => q.doc),
-            Int32Array.from(queries, (q) => (nil(q.start) ? 0 : Math.max(q.start, 0))),
-            Int32Array.from(queries, (q) => (nil(q.end) ? -1 : Math.max(q.end, 0))), 3);
+        const docs = Uint32Array.from(queries, (q) => q.doc);
+        const starts = Int32Array.from(queries, (q) => (nil(q.start) ? 0 : Math.max(q.start, 0)));
+        const ends = Int32Array.from(queries, (q) => (nil(q.end) ? -1 : Math.max(q.end, 0)));
+        const r = queries.some((q) => !nil(q.clientId) && q.clientId !== 0)
+            ? native.walkSegmentsView(this.h, docs, starts, ends, Int32Array.from(queries, (q) => (nil(q.refSeq) ? 0 : q.refSeq)),
+                Int32Array.from(queries, (q) => (nil(q.clientId) ? 0 : q.clientId)), 3)
+            : native.walkSegments(this.h, docs, starts, ends, 3);
         const w = r.rows;
         return queries.map((query, q) => {
             const view = this.client(query.doc);
@@ -743,6 +750,33 @@ class GpuClient {
                 return this._textRange(start, end, placeholder.length ? placeholder.charCodeAt(0) : 0);
             },
         };
+    }
+
+    /**
+     * MergeTreeTextHelper.getText(refSeq, clientId, placeholder, start, end) (textSegment.ts:
+     * 153-171) in any view the collab window holds, built here from one walk in the view as
+     * gatherText clips (textSegment.ts:241-263): a visited text gives all of itself when start <= 0
+     * and end >= its length, else substring(max(start, 0)) when end >= its length, else
+     * substring(start, end) -- which swaps the two when end < start; a marker gives the
+     * placeholder once per unit of its length.  The "*" placeholder is not offered.
+     */
+    getTextInView(refSeq, clientId, placeholder = "", start, end) {
+        if (typeof placeholder !== "string" || placeholder === "*") {
+            throw new Error("merge-tree replay: the marker placeholder is a string other than \"*\"");
+        }
+        let text = "";
+        this.mergeTree.mapRange({ leaf: (segment, pos, r, c, s, e) => {
+            if (segment.type === "Marker") {
+                text += placeholder.repeat(segment.cachedLength);
+            } else if (s <= 0 && e >= segment.text.length) {
+                text += segment.text;
+            } else {
+                const from = Math.max(s, 0);
+                text += e >= segment.text.length ? segment.text.substring(from) : segment.text.substring(from, e);
+            }
+            return true;
+        } }, refSeq, clientId, undefined, start, end);
+        return text;
     }
 
     /**
@@ -1025,6 +1059,34 @@ class GpuClient {
                     const r = native.getContainingSegment(h(), self.doc, pos, refSeq, clientId);
                     return r === null ? { segment: undefined, offset: undefined }
                         : { segment: self._segFromInfo(r), offset: r.offset };
+                },
+                // MergeTree.mapRange(actions, refSeq, clientId, accum, start, end, splitRange)
+                // (mergeTree.ts:2830-2840): the leaf action only, for every segment nodeMap visits
+                // in the view, until it returns a falsy value; one call on the device
+                mapRange(actions, refSeq, clientId, accum, start, end, splitRange = false) {
+                    if (splitRange) {
+                        throw new Error("merge-tree replay: mapRange with splitRange is not offered (it changes the replica)");
+                    }
+                    for (const k of ["pre", "post", "shift", "contains"]) {
+                        if (actions[k]) { throw new Error(`merge-tree replay: mapRange's ${k} action is not offered`); }
+                    }
+                    self._sync();
+                    for (const r of self.batch.walkSegments([{ doc: self.doc, start, end, refSeq, clientId }])[0]) {
+                        if (!actions.leaf(r.segment, r.pos, refSeq, clientId, r.start, r.end, accum)) { break; }
+                    }
+                },
+                // MergeTree.cloneSegments(refSeq, clientId, start = 0, end) (mergeTree.ts:1577-1599):
+                // copies of the segments the range visits in the view (the reference does not
+                // clip them); markers and texts with their properties
+                cloneSegments(refSeq, clientId, start = 0, end) {
+                    const out = [];
+                    this.mapRange({ leaf: (segment) => {
+                        const c = Object.assign({}, segment);
+                        if (segment.properties) { c.properties = Object.assign({}, segment.properties); }
+                        out.push(c);
+                        return true;
+                    } }, refSeq, clientId, undefined, start, end);
+                    return out;
                 },
                 get mergeTreeDeltaCallback() { return self.mergeTreeDeltaCallback; },
                 set mergeTreeDeltaCallback(f) { self.mergeTreeDeltaCallback = f; },

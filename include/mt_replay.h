@@ -576,8 +576,9 @@ typedef struct mt_walk_row {     /* 48 bytes */
                                     record of count 0) */
     int32_t start, end;          /* the leaf action's arguments: start[q] - position, end - position
                                     (not clipped to the segment) */
-    uint32_t flags;              /* 0 */
+    uint32_t flags;              /* MT_WALK_HOST, else 0 */
 } mt_walk_row;
+#define MT_WALK_HOST 1u          /* flags: the query was answered on the host (mt_walk_segments_view) */
 int mt_walk_segments(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
                      uint32_t what, int64_t *row_off, int64_t *text_off, int64_t *word_off, mt_walk_row *rows,
                      uint64_t cap_rows, uint16_t *text, uint64_t cap_text, uint32_t *records, uint64_t cap_words);
@@ -591,6 +592,39 @@ int mt_walk_segments_device(mt_handle *h, uint32_t n, const uint32_t *docs, cons
    makes the walk start at row 0 instead of at the page the directory names for start (the A/B
    of tools/walk_probe.py; results are identical). */
 int mt_last_walk_ms(mt_handle *h, float *out /* [2] */);
+/* ---- the walk in a (refSeq, client) view per query: MergeTree.mapRange(actions, refSeq, clientId,
+        accum, start, end) with a leaf action (MT/mergeTree.ts:2830-2840 -> nodeMap, :2936-2998).
+        ref_seq and client are both NULL (every query in the replica's own view) or both given;
+        client[q] == 0 is the replica's own view whatever ref_seq[q] holds, and such a query
+        answers exactly as mt_walk_segments does.  Otherwise ref_seq[q] must lie in the document's
+        [minSeq, currentSeq] (MT_E_INVALID, the message names the first such query); a negative
+        client is MT_E_INVALID before anything is launched.  Everything else -- arguments, errors,
+        sizing, MT_E_OVERFLOW, the record -- is mt_walk_segments'.
+        In the view a row's length is vl = (inserted and not removed in the view) ? length : 0
+        (nodeLength, :1692-1732) and position, start and end are in the view: the row at exclusive
+        vl-prefix pos is visited iff vl > 0, pos < end and pos + vl > start; an undefined end is
+        the view's length (mt_get_view_lengths_bulk's value).  That holds whenever the view's
+        length N = sum length * (ins - gone) equals L = sum vl, which every view at or above the
+        client's latest refSeq satisfies.  In a stale view with N != L the reference's interior
+        lengths differ from the sums of their leaves; such a query is answered on the host from
+        the tree's partial lengths, exactly as nodeMap walks them, and its rows carry
+        MT_WALK_HOST.  A remote query of a paged document decides N != L and seeks its first page
+        from the document's unsettled-segment table; a flat document's rows are walked from row 0.
+        On a live handle the view rule is mt_locate_segments'. ---- */
+int mt_walk_segments_view(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start, const int32_t *end,
+                          const int32_t *ref_seq, const int32_t *client, uint32_t what, int64_t *row_off,
+                          int64_t *text_off, int64_t *word_off, mt_walk_row *rows, uint64_t cap_rows, uint16_t *text,
+                          uint64_t cap_text, uint32_t *records, uint64_t cap_words);
+int mt_walk_segments_view_device(mt_handle *h, uint32_t n, const uint32_t *docs, const int32_t *start,
+                                 const int32_t *end, const int32_t *ref_seq, const int32_t *client, uint32_t what,
+                                 void *row_off_dev, void *text_off_dev, void *word_off_dev, void *rows_dev,
+                                 uint64_t cap_rows, void *text_dev, uint64_t cap_text, void *records_dev,
+                                 uint64_t cap_words);
+/* The last walk (either entry point): out[0] its queries, out[1] those answered on the host,
+   out[2] remote queries that started at the page the table-based seek found (MT_LOCATE_ROW_WALK=1:
+   none, every remote walk starts at row 0; results are identical); ms (nullable): the device
+   times of the counting pass and the gather, as mt_last_walk_ms. */
+int mt_last_walk_view(mt_handle *h, int64_t *out /* [3] */, float *ms /* [2] */);
 /* Debug: raw segment records (8 u32 per segment: segA then segB) and the 32-word header. */
 int mt_debug_raw(mt_handle *h, uint32_t doc, uint32_t *rows, uint32_t cap_rows, uint32_t *n_rows,
                  int32_t *hdr_words);
